@@ -1,10 +1,15 @@
 #!/usr/bin/env python
 """bench.py — measures BASELINE.json's metric on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (a plain `python bench.py --gpus N` with N > 1 starts its N ranks itself through torch.distributed.run — one process per GPU over
 RCCL — and fails loudly when fewer than N devices are visible; `n_gpus` in the line is always the number of ranks that ran)
+
+A plain run sets up, warms up, times the K steps of the headline and prints ONE JSON line (`metric`, `value`, `unit`,
+`ms_per_step` = milliseconds per timed step, ...); `--dump-outputs DIR` writes what the last timed step returned (dump_outputs).
+Everything else below (recall, roofline, cpu_baseline, dispersion, multi-stream runs, sweeps, the `workloads` block, the full
+record) runs with `--full` only.
 
 Headline (`value`, `ms_per_step`, `roofline`, `cpu_baseline` at the top level of the ONE JSON line) =
 BASELINE.json configs[1]: SIFT-1M-like 1M x 128 f32 (synthetic), HNSW ef=200, top-10, batch=64,
@@ -15,7 +20,7 @@ The graph of the headline is built the way MuopDB builds it (HnswBuilder::insert
 round 6); the bulk k-NN build is the workload `hnsw_c2_knn_graph`.  `value` is the K-step region's; `dispersion.long_region` adds one
 region of 200 steps (K = 20 steps are ~15 ms: inside the 3-8 % two boxes differ by).
 
-The same run also times the other north-star workloads and reports them under `workloads` (each entry with its own
+A --full run also times the other north-star workloads and reports them under `workloads` (each entry with its own
 value / ms_per_step / recall_at_10 / roofline / cpu_baseline, every one bracketed by the same barrier +
 synchronize and max-over-ranks rule):
     hnsw_c2_b1, hnsw_c2_ef400 the metric's other batch size / ef above 256, over the same resident graph
@@ -59,6 +64,8 @@ DISP_REGIONS = 4       # extra timed regions per workload for the dispersion ent
 WARM_MIN_S = 0.05      # Env.timed: the untimed warm-up lasts at least this long (the W steps repeated)
 PROF_EVERY = 8         # steps of the timed region between two steps whose dominant kernels are bracketed by HIP events
 METRIC = "QPS @ recall@10, SIFT-1M d=128 top-10, batch=1/64; 1/2/4/8 GPUs"
+FULL_JSON_DEFAULT = os.path.join("bench_out", "bench_full.json")   # --full: the full record, relative to the repository root
+DUMP_OUTPUTS_LIMIT = 64 << 20   # --dump-outputs: bytes in all; a larger output is cut to a fixed, seeded sample of its rows
 
 
 def measured_traffic(kind, cfg):
@@ -159,8 +166,15 @@ def parse():
     p.add_argument("--plan", action="store_true",
                    help="print what `--gpus N` (workload all) will build and hold — per workload: who builds, estimated build / load "
                         "seconds, host bytes private to a rank and shared through the page cache, HBM per rank — and exit (no GPU needed)")
-    p.add_argument("--full-json", default=None, help="where rank 0 writes the full record (default gpurun_out/bench_full.json); stdout "
-                                                     "carries ONE compact line of at most %d bytes" % LINE_LIMIT)
+    p.add_argument("--full", action="store_true",
+                   help="measure and check everything besides the headline timing: the `workloads` block, CPU baselines, recall, "
+                        "roofline brackets, dispersion regions, multi-stream runs, sweeps and the full record (off: set up, warm up, "
+                        "time the K steps, print the line)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the line's workload computed in its last timed step (ids, scores, counts) "
+                        "as DIR/<name>.npy in float32 / float64, at most %d MB in all" % (DUMP_OUTPUTS_LIMIT >> 20))
+    p.add_argument("--full-json", default=None, help="--full: where rank 0 writes the full record (default %s); stdout "
+                                                     "carries ONE compact line of at most %d bytes" % (FULL_JSON_DEFAULT, LINE_LIMIT))
     p.add_argument("--sift-clusters", type=int, default=None, help="SiftLike mixture components (generator exploration)")
     p.add_argument("--sift-sigma", type=float, default=None)
     p.add_argument("--sift-noise", type=float, default=None)
@@ -202,7 +216,8 @@ def cpu_baseline(single_fn, multi_fn, nq, seconds, probe, match_fn, sample_fmt):
 class Env:
     def __init__(self, args, ctx, rank, world):
         self.args, self.ctx, self.rank, self.world = args, ctx, rank, world
-        self.cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+        self.cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+        self.outputs = None        # --dump-outputs: host copies of the first timed region's last step (Env.timed)
         self._sift = None
         self._real = None
         self.hnsw_cache = {}
@@ -300,12 +315,14 @@ class Env:
             return float(t.item())
         return seconds
 
-    def timed(self, step, steps, warm, profiling=True, disperse=True, long_steps=0):
+    def timed(self, step, steps, warm, profiling=True, disperse=True, long_steps=0, outputs=None):
         """W untimed warm-up steps, then exactly K steps between barrier + synchronize; max over ranks.
         Returns (seconds, dominant-kernel ms summed, launches).  The region that is returned is the FIRST one; `last_dispersion`
         then holds how much the same K steps vary when repeated (a 17 ms region alone cannot tell a 3 % change
         from noise): DISP_REGIONS more regions bracketed the same way (region-level min / median / max of ms per step, the
-        returned region included), and one region with an event after every step on the launch stream (per-step GPU time)."""
+        returned region included), and one region with an event after every step on the launch stream (per-step GPU time).
+        The dispersion regions run with --full only.  outputs() -> {name: device tensor}: the buffers a step writes, copied to the
+        host right after the first region (its last step) for --dump-outputs, by the first workload of the run that passes them."""
         for i in range(warm):
             step(i)
         self.ctx.sync()
@@ -339,8 +356,10 @@ class Env:
         kernel_ms, launches = self.ctx.get_profile()
         self.ctx.set_profiling(False)
         elapsed = self.max_over_ranks(elapsed)
+        if outputs is not None and self.args.dump_outputs and self.outputs is None:
+            self.outputs = {name: t.cpu().numpy() for name, t in outputs().items()}
         self.last_dispersion = None
-        if disperse and steps > 0:
+        if disperse and self.args.full and steps > 0:
             regions = [1000 * elapsed / steps]
             for _ in range(DISP_REGIONS):
                 self.barrier()
@@ -514,9 +533,19 @@ def run_hnsw(env, batch=None, graph=None, n=None, extras=True, steps=None, warm=
             keep.append(ids[:, :, 0].clone())
 
     # the headline also runs one LONG region (>= 200 steps, the timed batches cycled): K = 20 steps are ~15 ms, inside the 3-8 % two
-    # boxes differ by, and a round-to-round delta of that size cannot be told from noise; `value` stays the K-step region's
-    elapsed, kernel_ms, launches = env.timed(step, steps, warm, long_steps=max(LONG_STEPS, steps) if extras else 0)
+    # boxes differ by, and a round-to-round delta of that size cannot be told from noise; `value` stays the K-step region's.
+    # Without --full the timed region carries no kernel brackets and nothing else follows it.
+    elapsed, kernel_ms, launches = env.timed(step, steps, warm, profiling=args.full, long_steps=max(LONG_STEPS, steps) if extras else 0,
+                                             outputs=lambda: dict(ids=ids, scores=sc, counts=cn))
     disp = env.last_dispersion
+    how = ("exact k-NN + select_neighbors_heuristic (bulk build)" if graph == "knn"
+           else "HnswBuilder::insert's algorithm, wave-batched (muopdb_amd.build.insert_hnsw, ef_construction=100)")
+    config = {"workload": "%s %dx%d f32 (%s); HNSW max_neighbors=%d ef=%d top-%d batch=%d per GPU; graph: %s; replicas"
+                          % ("SIFT-1M" if args.sift_dir else "SIFT-1M-like synthetic", n, d, desc, args.max_neighbors, ef, k, batch, how),
+              "n": n, "dim": d, "batch": batch, "ef": ef, "k": k, "index": "hnsw", "graph": graph,
+              "data": "sift1m" if args.sift_dir else args.data, "parallelism": "replica x%d" % world, "graph_build_s": build_s}
+    if not args.full:
+        return dict(value=world * steps * batch / elapsed, ms_per_step=1000 * elapsed / steps, config=config, steps=steps, warmup=warm)
     # untimed re-run of the timed batches: results for recall + exact traversal counters per launch
     found, evals, expanded, abytes = [], 0, 0, 0
     for i in range(warm, warm + steps):
@@ -527,14 +556,8 @@ def run_hnsw(env, batch=None, graph=None, n=None, extras=True, steps=None, warm=
     tq = queries[warm * batch:(warm + steps) * batch]
     gt, _ = S.exact_knn(x, k, queries=tq, f64=True)
     rec = recall_at_k(found, gt.cpu().numpy(), k)
-    how = ("exact k-NN + select_neighbors_heuristic (bulk build)" if graph == "knn"
-           else "HnswBuilder::insert's algorithm, wave-batched (muopdb_amd.build.insert_hnsw, ef_construction=100)")
     out = dict(
-        value=world * steps * batch / elapsed, ms_per_step=1000 * elapsed / steps, recall_at_10=rec,
-        config={"workload": "%s %dx%d f32 (%s); HNSW max_neighbors=%d ef=%d top-%d batch=%d per GPU; graph: %s; replicas"
-                            % ("SIFT-1M" if args.sift_dir else "SIFT-1M-like synthetic", n, d, desc, args.max_neighbors, ef, k, batch, how),
-                "n": n, "dim": d, "batch": batch, "ef": ef, "k": k, "index": "hnsw", "graph": graph,
-                "data": "sift1m" if args.sift_dir else args.data, "parallelism": "replica x%d" % world, "graph_build_s": build_s},
+        value=world * steps * batch / elapsed, ms_per_step=1000 * elapsed / steps, recall_at_10=rec, config=config,
         # ef <= 448: the traversal is three kernels — the upper layers' distance table (fused with the top layers' traversal — on sorted
         # positions since round 6, mdb_hnsw_rank.hip.h — for batches >= 32), layer 1's single-wave traversal and the layer-0 instance of
         # the beam kernel (mdb_hnsw_upper.hip); the bracket is their sum, the algorithmic bytes are the whole traversal's
@@ -630,7 +653,7 @@ def run_flat(env, n=None, batch=None, steps=None, warm=None):
     def step(i):
         idx.search_device(queries[i * batch:(i + 1) * batch].data_ptr(), batch, k, ids.data_ptr(), ds.data_ptr())
 
-    elapsed, kernel_ms, launches = env.timed(step, steps, warm)
+    elapsed, kernel_ms, launches = env.timed(step, steps, warm, outputs=lambda: dict(ids=ids, scores=ds))
     disp = env.last_dispersion
     abytes = (hi - lo) * d * 4 + batch * d * 4 + batch * k * 8
     # recall@k of the last timed batch against the f64 brute force (untimed re-run of that batch)
@@ -734,7 +757,8 @@ def ivfpq_measure(env, ivf, x, queries, batch, k, P, steps, warm, gt=None, nrec=
         if keep is not None:
             keep.append(res[:, :, 0].clone())
 
-    elapsed, kernel_ms, launches = env.timed(step, steps, warm, disperse=disperse)
+    outputs = (lambda: dict(ids=ids, scores=sc, counts=cn)) if world == 1 else None
+    elapsed, kernel_ms, launches = env.timed(step, steps, warm, disperse=disperse, outputs=outputs)
     disp = env.last_dispersion
     found, scored, abytes = [], 0, 0
     for i in range(warm, warm + steps):
@@ -818,7 +842,7 @@ def run_ivfpq(env, shard=None, no_sweep=False):
     if m.get("rows_equal_across_ranks") is not None:
         out["rows_equal_across_ranks"] = m["rows_equal_across_ranks"]
     out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic("ivfpq", out["config"])
-    if args.streams > 1 and world == 1:
+    if args.full and args.streams > 1 and world == 1:
         # Extra: the same batches round-robin on several HIP streams, each through its own handle ATTACHED to the one resident
         # index (mdb_ivf_attach: shared posting lists / tombstones, own scratch + stream) — several batches in flight.
         from muopdb_amd import lib as L
@@ -851,7 +875,7 @@ def run_ivfpq(env, shard=None, no_sweep=False):
                                  note="same batches, several in flight on handles attached to ONE resident index; not the workload's value")
         for lane_ in lanes:
             lane_[2].close(); lane_[1].close()
-    if not (args.no_sweep or no_sweep):
+    if args.full and not (args.no_sweep or no_sweep):
         sweep = []
         for p in (1, 8, 16, 32, 64):
             if p > nlist:
@@ -1213,7 +1237,8 @@ def run_spann(env, users=None, no_sweep=False, steps=None, warm=None, shard=None
             if keep is not None:
                 keep.append(res[:, :, 0].clone())
 
-        elapsed, kernel_ms, launches = env.timed(step, steps, warm, profiling=1, disperse=disperse)  # 1: posting-list scan only
+        outputs = (lambda: dict(ids=ids, scores=sc, counts=cn)) if world == 1 else None
+        elapsed, kernel_ms, launches = env.timed(step, steps, warm, profiling=1, disperse=disperse, outputs=outputs)  # 1: posting-list scan only
         disp = env.last_dispersion
         found, scored, abytes, evals, expanded = [], 0, 0, 0, 0
         ctx.set_profiling(2); ctx.get_profile()  # untimed re-run: centroid-graph traversal kernel time
@@ -1256,7 +1281,7 @@ def run_spann(env, users=None, no_sweep=False, steps=None, warm=None, shard=None
         out["rows_equal_across_ranks"] = m["rows_equal_across_ranks"]
     out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic("spann_full" if U >= 1024 else "spann", out["config"])
     out["steps"], out["warmup"] = steps, warm
-    if not (args.no_sweep or no_sweep):
+    if args.full and not (args.no_sweep or no_sweep):
         sweep = []
         for p_, r_ in ((4, 0.1), (16, 0.1), (64, 0.1), (4, 0.3), (16, 0.3), (64, 0.3), (16, 1.0)):
             s = m if (p_, r_) == (P, ratio) else measure(p_, r_, disperse=False)
@@ -1397,9 +1422,13 @@ def short_workload(cfg):
 
 
 def emit(args, line):
-    """rank 0: the full record (every workload's config prose, dispersion, sweeps, notes) goes to --full-json (default
-    gpurun_out/bench_full.json when that directory can be made) and to stderr; stdout gets exactly ONE bounded line."""
-    path = args.full_json or os.path.join(ROOT, "gpurun_out", "bench_full.json")
+    """rank 0: with --full, the full record (every workload's config prose, dispersion, sweeps, notes) goes to --full-json (default
+    FULL_JSON_DEFAULT under the repository root, when that directory can be made) and to stderr; stdout gets exactly ONE bounded line."""
+    if not args.full:
+        sys.stdout.write(compact_line(line) + "\n")
+        sys.stdout.flush()
+        return
+    path = args.full_json or os.path.join(ROOT, FULL_JSON_DEFAULT)
     try:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
@@ -1411,6 +1440,26 @@ def emit(args, line):
     sys.stderr.flush()
     sys.stdout.write(compact_line(line) + "\n")
     sys.stdout.flush()
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: the arrays Env.timed kept from the last step of the first timed region, as DIR/<name>.npy — integers as
+    float64 (exact below 2^53: doc ids, counts), floats as float32.  Above DUMP_OUTPUTS_LIMIT bytes in all, the same fixed, seeded
+    sample of rows (first axis) is taken from every array, and rows.npy says which."""
+    if outputs is None:
+        sys.stderr.write("bench.py: --dump-outputs: this workload keeps no outputs of its timed steps\n")
+        sys.exit(2)
+    arrs = {name: a.astype(np.float32 if a.dtype.kind == "f" else np.float64) for name, a in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_OUTPUTS_LIMIT:
+        n = min(a.shape[0] for a in arrs.values())
+        rows = np.sort(np.random.default_rng(0).choice(n, size=max(1, n * DUMP_OUTPUTS_LIMIT // (2 * total)), replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+    log("outputs of the last timed step: %s in %s" % (", ".join("%s%s" % (k_, list(a.shape)) for k_, a in arrs.items()), directory))
 
 
 def launch_ranks(args):
@@ -1541,7 +1590,7 @@ def main():
         if world == 1 and not args.no_insert_graph:  # C2 again on the graph built the other way (default: the bulk k-NN build next to the insert-built headline)
             other = "knn" if args.graph == "insert" else "insert"
             plan.append(("hnsw_c2_%s_graph" % other, lambda: run_hnsw(env, batch=64, graph=other, n=args.insert_n, extras=False)))
-        for name, fn in plan:
+        for name, fn in (plan if args.full else []):   # the other workloads: --full only
             t0 = time.time()
             try:  # a failing extra workload must never take the headline line with it
                 torch.cuda.empty_cache()
@@ -1553,7 +1602,10 @@ def main():
             except Exception as e:  # noqa: BLE001
                 extra[name] = {"error": "%s: %s" % (type(e).__name__, e)}
             log("%s: %.1fs" % (name, time.time() - t0))
-        res["workloads"] = extra
+        if args.full:
+            res["workloads"] = extra
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env.outputs)
     env.drop_kept_builds()
     for h in env.hnsw_cache.values():
         h[0].close()

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/ab_units; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 DUMP=/tmp/mdb_dump_ab
-timeout 900 python $REPO/bench.py --workload spann --users 1024 --no-sweep --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP/c4full --dump-big > $OUT/c4full_bench.json 2> $OUT/c4full_bench.err
+timeout 900 python $REPO/bench.py --full --workload spann --users 1024 --no-sweep --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP/c4full --dump-big > $OUT/c4full_bench.json 2> $OUT/c4full_bench.err
 for rep in 1 2; do for V in 0 1; do
   rm -rf /tmp/prof_ab
   MDB_SCAN_F32_UNIT_ONLY=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ab -o r -- $REPO/muopdb_amd/replay_search mspann $DUMP/c4full/spann 768 10 16 1024 10 200 > $OUT/c4_$V_$rep.log 2>&1

@@ -5,7 +5,7 @@ OUT=$REPO/gpurun_out/c1; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for V in ${VARIANTS:-0 4 1}; do
   rm -rf /tmp/prof_c1_$V
-  MDB_FLAT_NO_SMALL=$V timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c1_$V -o b -- python $REPO/bench.py --workload flat --n 10000 --batch 1 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_$V.log 2>&1
+  MDB_FLAT_NO_SMALL=$V timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c1_$V -o b -- python $REPO/bench.py --full --workload flat --n 10000 --batch 1 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_$V.log 2>&1
   cp /tmp/prof_c1_$V/*kernel_stats.csv $OUT/kernel_stats_$V.csv
   echo "== MDB_FLAT_NO_SMALL=$V"; grep -o '"ms_per_step":[0-9.e-]*' $OUT/bench_$V.log | head -1
   python3 - $OUT/kernel_stats_$V.csv <<'PY'

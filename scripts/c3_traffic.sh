@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 D=/tmp/mdb_dump_c3
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py --workload ivfpq --no-sweep --streams 0 --no-cpu-baseline --steps 20 --warmup 5 --dump-dir $D > /dev/null 2>&1
+python $REPO/bench.py --full --workload ivfpq --no-sweep --streams 0 --no-cpu-baseline --steps 20 --warmup 5 --dump-dir $D > /dev/null 2>&1
 for v in "X=1" "MDB_PQ_SDC_MAX_MB=0" "MDB_IVF_COARSE_MFMA=0" "MDB_PQF_TILES=1"; do
   for C in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pc3

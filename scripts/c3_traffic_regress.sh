@@ -1,7 +1,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 D=/tmp/mdb_dump_c3
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py --workload ivfpq --no-sweep --streams 0 --no-cpu-baseline --steps 20 --warmup 5 --dump-dir $D > /dev/null 2>&1
+python $REPO/bench.py --full --workload ivfpq --no-sweep --streams 0 --no-cpu-baseline --steps 20 --warmup 5 --dump-dir $D > /dev/null 2>&1
 for P in 1 4 16 64; do
     rm -rf /tmp/pc3
     MDB_PQ_SDC_MAX_MB=0 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pc3 -o r -- $REPO/muopdb_amd/replay_search ivfpq $D/ivfpq 128 10 $P 256 20 > /tmp/pc3.log 2>&1

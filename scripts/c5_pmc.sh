@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 --list-avail > $OUT/avail.txt 2>&1
 grep -o "SQ_[A-Z_0-9]*" $OUT/avail.txt | sort -u | tr '\n' ' ' > $OUT/sq_counters.txt
 if [ ! -d $DUMP/c5 ]; then
-  timeout 900 python $REPO/bench.py --workload c5 --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+  timeout 900 python $REPO/bench.py --full --workload c5 --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 fi
 i=0
 for G in "$@"; do

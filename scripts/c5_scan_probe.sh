@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
 DUMP=/tmp/mdb_dump_c5
 cd /tmp && export TMPDIR=/tmp
 if [ ! -d $DUMP/c5 ]; then
-  timeout 900 python $REPO/bench.py --workload c5 --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+  timeout 900 python $REPO/bench.py --full --workload c5 --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 fi
 for P in "$@"; do
   rm -rf /tmp/prof_c5_p$P

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
 DUMP=/tmp/mdb_dump_flat
 cd /tmp && export TMPDIR=/tmp
-timeout 300 python $REPO/bench.py --workload flat --n 1000000 --batch 64 --steps 20 --warmup 5 --no-cpu-baseline --dump-dir $DUMP > $OUT/bench_flat.json 2> $OUT/bench_flat.err
+timeout 300 python $REPO/bench.py --full --workload flat --n 1000000 --batch 64 --steps 20 --warmup 5 --no-cpu-baseline --dump-dir $DUMP > $OUT/bench_flat.json 2> $OUT/bench_flat.err
 ls $DUMP
 for V in cur other; do
   P=""; [ $V = other ] && P=$OTHER

@@ -5,6 +5,6 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 cp muopdb_amd/libmuopdb_hip.so /tmp/lib_a.so; cp ab/libmuopdb_hip.so muopdb_amd/libmuopdb_hip.so
 for D in 1 2; do
   echo "MDB_HNSW_DBG=$D"
-  MDB_HNSW_DBG=$D python bench.py --workload hnsw --streams 0 --no-cpu-baseline --no-sweep --no-insert-graph --steps 4 --warmup 1 2>&1 | grep "hnsw dbg" | tail -2
+  MDB_HNSW_DBG=$D python bench.py --full --workload hnsw --streams 0 --no-cpu-baseline --no-sweep --no-insert-graph --steps 4 --warmup 1 2>&1 | grep "hnsw dbg" | tail -2
 done
 cp /tmp/lib_a.so muopdb_amd/libmuopdb_hip.so

@@ -5,7 +5,7 @@ export MDB_BENCH_DEVICE=0 MDB_BENCH_BACKEND=gloo MDB_BENCH_WATCHDOG=200
 PORT=29517
 for a in "--workload spann --users 64 --shard users --no-sweep" "--workload spann --users 64 --shard lists --no-sweep" "--workload ivfpq --shard batch --no-sweep --base-n 200000" "--workload c5full --base-n 3000000 --shard batch" "--workload c5full --base-n 3000000 --shard lists"; do
   PORT=$((PORT+1))
-  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline --streams 0 $a 2>/tmp/mr.err | tail -1 | python -c "
+  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline --streams 0 $a 2>/tmp/mr.err | tail -1 | python -c "
 import sys,json
 l=sys.stdin.read().strip()
 try:

@@ -14,7 +14,7 @@ DUMP=/tmp/mdb_dump_$TAG
 PAT="hnsw_|flat_scan|flat_mfma|flat_refine|ivf_scan"
 rm -rf $OUT $DUMP; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_$TAG -o bench -- python $REPO/bench.py --no-cpu-baseline --dump-dir $DUMP "$@" > $OUT/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_$TAG -o bench -- python $REPO/bench.py --full --no-cpu-baseline --dump-dir $DUMP "$@" > $OUT/bench_stats.log 2>&1
 cp /tmp/prof_stats_$TAG/*kernel_stats.csv $OUT/ 2>/dev/null
 for f in /tmp/prof_stats_$TAG/*kernel_trace.csv; do [ -f "$f" ] && (head -1 $f; grep -E "$PAT" $f | head -300) > $OUT/kernel_trace_dominant.csv; done
 # uninstrumented replay first (checksum + host-buffer ms/step), then the counter passes

@@ -20,7 +20,7 @@ PAT="ivf_coarse|hnsw_|flat_scan|flat_mfma|flat_bf16|flat_refine|sample_bound|ivf
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # every workload's files + the un-instrumented bench line
-(time timeout 900 python $REPO/bench.py --steps 20 --warmup 5 --dump-dir $DUMP) > $OUT/bench_all.json 2> $OUT/bench_all.err
+(time timeout 900 python $REPO/bench.py --full --steps 20 --warmup 5 --dump-dir $DUMP) > $OUT/bench_all.json 2> $OUT/bench_all.err
 for W in $WL; do
   case $W in
     # (round 6: the headline graph is built by insertion ON THE GPU — thousands of searches through the same kernels at other shapes — so the
@@ -33,14 +33,14 @@ for W in $WL; do
     spann)    SUB=spann;    REPLAY="mspann $DUMP/spann 768 10 16 128 20 200"; BARGS="--workload spann --users 128 --no-sweep";;
     c5)       SUB=c5;       REPLAY="ivfpq $DUMP/c5 128 10 64 4096 6 0 8";     BARGS="";;   # the whole index's files, rank 0 of 8's share loaded
     c5full)   SUB=c5full;   REPLAY="ivfpq $DUMP/c5full/c5full 128 10 64 4096 6"; BARGS="";
-              (time timeout 1200 python $REPO/bench.py --workload c5full --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP/c5full) > $OUT/c5full_bench.json 2> $OUT/c5full_bench.err;;
+              (time timeout 1200 python $REPO/bench.py --full --workload c5full --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP/c5full) > $OUT/c5full_bench.json 2> $OUT/c5full_bench.err;;
     c4full)   SUB=spann;    REPLAY="mspann $DUMP/c4full/spann 768 10 16 1024 6 200"; BARGS="";
               df -h /tmp | tail -1 > $OUT/c4full_df.log
-              (time timeout 900 python $REPO/bench.py --workload spann --users 1024 --no-sweep --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP/c4full --dump-big) > $OUT/c4full_bench.json 2> $OUT/c4full_bench.err;;
+              (time timeout 900 python $REPO/bench.py --full --workload spann --users 1024 --no-sweep --steps 6 --warmup 2 --no-cpu-baseline --dump-dir $DUMP/c4full --dump-big) > $OUT/c4full_bench.json 2> $OUT/c4full_bench.err;;
   esac
   if [ -n "$BARGS" ]; then
     rm -rf /tmp/prof_stats_$W
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_$W -o bench -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline $BARGS > $OUT/${W}_bench_stats.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats_$W -o bench -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $BARGS > $OUT/${W}_bench_stats.log 2>&1
     cp /tmp/prof_stats_$W/*kernel_stats.csv $OUT/${W}_kernel_stats.csv 2>/dev/null
   fi
   $REPO/muopdb_amd/replay_search $REPLAY > $OUT/${W}_replay.log 2>&1

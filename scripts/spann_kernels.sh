@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -o b -- python $REPO/bench.py --workload spann --users 128 --no-sweep --no-cpu-baseline --steps 20 --warmup 5 > /dev/null 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps -o b -- python $REPO/bench.py --full --workload spann --users 128 --no-sweep --no-cpu-baseline --steps 20 --warmup 5 > /dev/null 2>&1
 python3 - <<'P'
 import csv, glob
 for f in glob.glob("/tmp/ps/*kernel_stats.csv"):

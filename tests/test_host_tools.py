@@ -156,3 +156,51 @@ def test_bench_final_line_is_bounded_and_parses():
         plain = json.load(f)
     line = json.loads(bench.compact_line(plain))
     assert set(line["workloads"]) == set(plain["workloads"]) and "workloads_truncated" not in line
+
+
+def test_bench_dump_outputs_dtypes_and_seeded_sample(tmp_path):
+    """--dump-outputs: integers as float64, floats as float32, one .npy per array; above the byte limit the SAME seeded rows of
+    every array (rows.npy names them), identical from run to run; a workload without outputs is a loud error."""
+    bench, _ = _load_bench()
+    rng = np.random.default_rng(3)
+    outs = dict(ids=rng.integers(0, 1 << 40, (64, 10, 2)).astype(np.int64), scores=rng.standard_normal((64, 10)).astype(np.float32),
+                counts=np.full(64, 10, np.int32))
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("ids", "scores", "counts")}
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"].astype(np.int64), outs["ids"])
+    assert got["scores"].dtype == np.float32 and got["scores"].tobytes() == outs["scores"].tobytes()
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"], outs["counts"])
+    assert not (tmp_path / "a" / "rows.npy").exists()
+    bench.DUMP_OUTPUTS_LIMIT = 4096
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), outs)
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert 0 < len(rows) < 64 and np.all(np.diff(rows) > 0)
+    total = 0
+    for n in ("ids", "scores", "counts", "rows"):
+        a, b = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        assert a.tobytes() == b.tobytes() and a.shape[0] == len(rows)
+        total += a.nbytes
+    assert total <= 4096
+    assert np.array_equal(np.load(tmp_path / "b" / "ids.npy"), outs["ids"][rows.astype(np.int64)].astype(np.float64))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "d"), None)
+
+
+def test_bench_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """A plain run's line carries the headline's contract fields; --full, --dump-outputs default off."""
+    import json
+    bench, _ = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+    line = {"metric": bench.METRIC, "value": 83668.79, "unit": "queries/s", "n_gpus": 1, "steps": 7, "warmup": 2, "ms_per_step": 0.7649,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "x", "n": 1000000, "dim": 128, "batch": 64, "ef": 200, "k": 10, "index": "hnsw"}}
+    out = json.loads(bench.compact_line(line))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert out[key] == line[key], key
+    assert "workloads" not in out
