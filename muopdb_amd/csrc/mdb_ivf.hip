@@ -2607,7 +2607,7 @@ mdb_status IvfSet::search_fused(const float* d_q, int qstride, size_t b, const u
     fa.b = (uint32_t)b;
     fa.m = (uint32_t)pq.m;
     fa.tile_groups = (fa.cent_ntiles + 3) / 4;
-    fa.no_masks = (!f.allow && (root ? root : this)->tomb_any.load() == 0u) ? 1u : 0u;
+    fa.no_masks = (!f.allow && (root ? root : this)->tomb_any.load() == 0u && !ctx->opt.scan_masks_always) ? 1u : 0u;
     // coarse search of this step: 0 probes given, 1 every distance exactly (ivf_prep_kernel -> [B][L]), 2 matrix-core filter + candidates
     int coarse_mode = !coarse_here ? 0
                       : cm_usable(cmf, ctx, d_q, qstride, b, num_probes) ? 2 : 1;

@@ -148,6 +148,40 @@ def test_c2_hnsw_1m_ef200(ctx, oracle, base, flat_1m, hnsw_1m):
     assert (st_w["distance_evals"], st_w["expanded_nodes"]) == tuple(o.stats())          # ... and its traversal, step for step
 
 
+@pytest.fixture(scope="module")
+def hnsw_insert_1m(ctx, base):
+    """the bench headline's graph (bench.py --graph insert): built by insertion with bench.py's parameters"""
+    from muopdb_amd import build as B
+    from muopdb_amd.index import BlockBasedHnsw
+    idx, vec = B.hnsw_files_by_insertion(ctx, base[0], max_neighbors=32, max_layers=8, ef_construction=100, seed=1)
+    return idx, vec, BlockBasedHnsw(ctx, idx, vec, D)
+
+
+def test_c2_hnsw_1m_insertion_graph_ef200(ctx, oracle, base, hnsw_insert_1m):
+    """the insertion-built 1 M graph at ef 200: all 64 rows, score bits and (distance_evals, expanded_nodes) equal the oracle's, also with
+    the upper layers on sorted positions for no launch / both launches (MDB_HNSW_RANK 0 / 3), and any batch split gives the same rows"""
+    _, xh, q = base
+    idx, vec, g = hnsw_insert_1m
+    res = g.ann_search(q[:64], K, 200)
+    st = ctx.stats()
+    assert all(int(c) == K for c in res.counts[:64])
+    whole = rows_of(res, 64)
+    o = oracle.BlockBasedHnsw(idx, vec, D)
+    o.stats()
+    ores = o.ann_search(q[:64], K, 200, threads=_threads(oracle))
+    evals, expanded = o.stats()
+    assert rows_of(ores, 64) == whole
+    assert (st["distance_evals"], st["expanded_nodes"]) == (evals, expanded)
+    for value in (0, 3):
+        with ctx.option("MDB_HNSW_RANK", value):
+            rres = g.ann_search(q[:64], K, 200)
+            st = ctx.stats()
+        assert rows_of(rres, 64) == whole, value
+        assert (st["distance_evals"], st["expanded_nodes"]) == (evals, expanded), value
+    for lo, hi in [(0, 1), (1, 9), (9, 64)]:                                             # batches of 1, 8 and 55
+        assert rows_of(g.ann_search(q[lo:hi], K, 200), hi - lo) == whole[lo:hi], (lo, hi)
+
+
 def test_c3_ivfpq_1m_nprobe16(ctx, oracle, base):
     import torch
     from muopdb_amd import build as B, synth as S
