@@ -2439,7 +2439,13 @@ mdb_status IvfSet::scan(const float* d_q, int qstride, size_t b, const uint32_t*
                 a, d_codes.p, pq.m, pq.num_bits, pq.codebook.p, (uint8_t*)qcodes);                               \
         }                                                                                                            \
     } while (0)
-#define MDB_PQ2_LAUNCH(METRIC, SD, MWT) do { if (pq_full) MDB_PQ2_LAUNCH_F(METRIC, SD, MWT, true); else MDB_PQ2_LAUNCH_F(METRIC, SD, MWT, false); } while (0)
+// (whole-word 8-bit codes mean K = 256 and m = 4 MW: a codebook of SD * MW * 4 KB, which fits pq2_lds up to SD * MW = 32 — the wider
+// FULL instantiations could never be selected and are not compiled)
+#define MDB_PQ2_LAUNCH(METRIC, SD, MWT)                                                          \
+    do {                                                                                         \
+        if (!pq_full) MDB_PQ2_LAUNCH_F(METRIC, SD, MWT, false);                                  \
+        else if constexpr ((SD) * (MWT) <= 32) MDB_PQ2_LAUNCH_F(METRIC, SD, MWT, true);          \
+    } while (0)
 #define MDB_PQ2_SD(METRIC, MWT)                                                                                      \
     do {                                                                                                             \
         if (pq.subdim == 4) MDB_PQ2_LAUNCH(METRIC, 4, MWT);                                                          \
@@ -2487,12 +2493,12 @@ mdb_status IvfSet::scan(const float* d_q, int qstride, size_t b, const uint32_t*
             MDB_HIP(ctx, hipGetLastError());
 #define MDB_PQ3_REF(SD, MWT)                                                                                                      \
     do {                                                                                                                          \
-        if (pq_full)                                                                                                              \
-            ivf_pq3_refine_kernel<SD, MWT, true><<<dim3((unsigned)b), 256, ldsr, ctx->stream>>>(a, d_codes.p, pq.m, pq.num_bits, pq.codebook.p, \
-                                                                                                  (uint8_t*)qcodes, c3, ns3);              \
-        else                                                                                                                      \
+        if (!pq_full)                                                                                                             \
             ivf_pq3_refine_kernel<SD, MWT, false><<<dim3((unsigned)b), 256, ldsr, ctx->stream>>>(a, d_codes.p, pq.m, pq.num_bits, pq.codebook.p, \
                                                                                                    (uint8_t*)qcodes, c3, ns3);             \
+        else if constexpr ((SD) * (MWT) <= 32)   /* (as MDB_PQ2_LAUNCH: pq2, and so pq3, is off beyond) */                        \
+            ivf_pq3_refine_kernel<SD, MWT, true><<<dim3((unsigned)b), 256, ldsr, ctx->stream>>>(a, d_codes.p, pq.m, pq.num_bits, pq.codebook.p, \
+                                                                                                  (uint8_t*)qcodes, c3, ns3);              \
     } while (0)
 #define MDB_PQ3_REF_SD(MWT)                                                      \
     do {                                                                         \
@@ -2682,9 +2688,9 @@ mdb_status IvfSet::search_fused(const float* d_q, int qstride, size_t b, const u
     } while (0)
 #define MDB_PQF_CO(SD, MWT)                                      \
     do {                                                         \
-        if (coarse_mode == 2) MDB_PQF_LAUNCH(SD, MWT, 2);        \
-        else if (coarse_mode == 1) MDB_PQF_LAUNCH(SD, MWT, 1);   \
-        else MDB_PQF_LAUNCH(SD, MWT, 0);                         \
+        if (coarse_mode == 1) MDB_PQF_LAUNCH(SD, MWT, 1);        \
+        else if (coarse_mode == 0) MDB_PQF_LAUNCH(SD, MWT, 0);   \
+        else if constexpr (cm_dim_ok((SD) * 4 * (MWT))) MDB_PQF_LAUNCH(SD, MWT, 2);   /* (d = SD * 4 MW here: cm_build serves no other) */ \
     } while (0)
 #define MDB_PQF_SD(MWT)                                       \
     do {                                                      \

@@ -640,7 +640,7 @@ __global__ __launch_bounds__(256) void cm_frag_kernel(const float4* __restrict__
     chi[o] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
 }
 
-static inline bool cm_dim_ok(uint32_t d) { return d == 64 || d == 96 || d == 128 || d == 192 || d == 256; }
+static constexpr bool cm_dim_ok(uint32_t d) { return d == 64 || d == 96 || d == 128 || d == 192 || d == 256; }
 
 // cv: the centroid tiles of the (single) index.  Leaves `cm` empty when the shape is not served or memory is short (the fused step
 // then keeps ivf_prep_kernel: an optional accelerator never fails a load).

@@ -1,8 +1,70 @@
 """Test-side index synthesis (numpy): deterministic k-means, PQ codebooks, IVF / SPANN /
 multi-user segment assembly in the reference's on-disk formats (muopdb_amd.formats)."""
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
 
 from muopdb_amd import formats as F
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+
+def have_llvm_tools(*tools):
+    return all(os.path.exists(os.path.join(LLVM, t)) for t in (tools or ("llvm-objdump",)))
+
+
+def extract_code_objects(lib_path, workdir):
+    """Copies the shared library into `workdir`, unbundles its device code there (llvm-objdump --offloading) and returns the file
+    names (relative to `workdir`) of its gfx950 code objects.  No GPU needed."""
+    workdir = str(workdir)
+    so = os.path.join(workdir, os.path.basename(lib_path))
+    shutil.copy(lib_path, so)
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", os.path.basename(so)], cwd=workdir, check=True, capture_output=True)
+    return sorted(f for f in os.listdir(workdir) if f.endswith("gfx950"))
+
+
+def disassemble(workdir, obj):
+    return subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", obj], cwd=str(workdir), check=True, capture_output=True, text=True).stdout
+
+
+def kernel_key(name):
+    """A kernel's demangled name without return type, parameter list and descriptor suffix: `ivf_scan_pq3_kernel<4, 512, true>`.
+    The same key comes out of a `.kd` symbol of a code object and of a profiler's kernel name."""
+    name = re.sub(r"\s*(\(\.kd\)|\[clone \.kd\]|\.kd)\s*$", "", name.strip())
+    depth, cut = 0, len(name)
+    for i, ch in enumerate(name):
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0:
+            cut = i
+            break
+    name = name[:cut].strip()
+    if name.startswith("void "):
+        name = name[5:]
+    return re.sub(r"\s+", " ", name).replace(" >", ">")
+
+
+def is_project_kernel(key):
+    """everything but the library kernels that come in with rocprim"""
+    return not key.startswith("rocprim::")
+
+
+def library_kernels(lib_path, workdir):
+    """keys (kernel_key) of every kernel descriptor in the gfx950 code objects of `lib_path`, library kernels included"""
+    keys = set()
+    for obj in extract_code_objects(lib_path, workdir):
+        out = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--symbols", "--demangle", "-W", obj], cwd=str(workdir), check=True,
+                             capture_output=True, text=True).stdout
+        for line in out.splitlines():
+            f = line.split(None, 7)
+            if len(f) == 8 and f[3] == "OBJECT" and re.search(r"(\(\.kd\)|\.kd)\s*$", f[7]):
+                keys.add(kernel_key(f[7]))
+    return keys
 
 
 def kmeans(x, k, iters=10, seed=0):

@@ -382,7 +382,8 @@ def test_ivf_assign_matches_builder_rule(ctx, oracle, n, d, L, mc, thr):
 
 
 # ----------------------------------------------------------------------------------- IVF (I1-I3)
-def _ivf_case(oracle, ctx, n, d, L, seed, quant=None, cpv=1, doc_base=100):
+def _ivf_case(oracle, ctx, n, d, L, seed, quant=None, cpv=1, doc_base=100, metric=0):
+    """metric: of the PQ quantizer (0 = L2, 1 = dot); f32 lists keep the loader's default"""
     from muopdb_amd.index import BlockBasedIvf, ProductQuantizer
     rng = np.random.default_rng(seed)
     v = H.sift_like(n, d, n_clusters=max(L // 2, 1), seed=seed)
@@ -393,8 +394,8 @@ def _ivf_case(oracle, ctx, n, d, L, seed, quant=None, cpv=1, doc_base=100):
         cb = H.train_pq_codebook(v[: min(n, 2000)], sub, bits, iters=3)
         opq = oracle.ProductQuantizer(d, sub, bits, cb)
         index, vec, pls = H.build_ivf_files(v, doc_ids, c, quantize=opq.quantize, clusters_per_vector=cpv)
-        oq = oracle.Quant(oracle.QUANT_PQ, oracle.METRIC_L2, sub, bits, cb)
-        gq = ProductQuantizer(d, sub, bits, cb)
+        oq = oracle.Quant(oracle.QUANT_PQ, oracle.METRIC_DOT if metric else oracle.METRIC_L2, sub, bits, cb)
+        gq = ProductQuantizer(d, sub, bits, cb, metric)
     else:
         index, vec, pls = H.build_ivf_files(v, doc_ids, c, clusters_per_vector=cpv)
         oq, gq = None, None

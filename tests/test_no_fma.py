@@ -10,16 +10,13 @@ Two fused forms are legitimate inside the exact kernels and are recognised by sh
     operand — an accumulate step `acc += d * d` never has one);
   * the u64 <-> f32 conversions of integer division (`v_fmamk_f32 .., 0x4f800000 / 0xcf800000` = +-2^32, or a literal 0
     multiplier, next to v_rcp)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from muopdb_amd import lib as L
+from tests import helpers as H
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 FUSED = re.compile(r"\b(v_fma_f|v_fmac_f|v_mad_f|v_mac_f|v_pk_fma|v_pk_mad|v_fmaak|v_fmamk|v_madak|v_madmk|v_dot\d|v_mfma)")
 # kernels whose results carry the reference's lane association (every distance that is RETURNED or RANKED exactly)
 EXACT = re.compile(r"(flat_scan_kernel|flat_small_scan_kernel|flat_small_block_kernel|flat_refine_kernel|ivf_scan_f32_kernel|ivf_scan_pq2?_kernel|ivf_pq3_refine_kernel|ivf_pq_fused_kernel|ivf_prep_kernel|ivf_coarse_rank_kernel|merge_rows_remap_kernel|"
@@ -34,16 +31,13 @@ NO_FLAT = re.compile(r"(ivf_scan_pq3_kernel|ivf_pq3_refine_kernel|ivf_scan_pq2_k
                      r"flat_refine_kernel|sample_bound_kernel)")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-objdump")), reason="llvm-objdump not installed")
+@pytest.mark.skipif(not H.have_llvm_tools(), reason="llvm-objdump not installed")
 def test_exact_kernels_contain_no_fused_multiply_add(tmp_path):
-    so = tmp_path / "libmuopdb_hip.so"
-    shutil.copy(L.LIB_PATH, so)
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so.name], cwd=tmp_path, check=True, capture_output=True)
-    objs = [f for f in os.listdir(tmp_path) if f.endswith("gfx950")]
+    objs = H.extract_code_objects(L.LIB_PATH, tmp_path)
     assert objs, "no gfx950 code object inside libmuopdb_hip.so"
     kernels, offenders, explained = 0, [], 0
     for f in objs:
-        asm = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", f], cwd=tmp_path, check=True, capture_output=True, text=True).stdout
+        asm = H.disassemble(tmp_path, f)
         cur = None
         seen = set()
         recent = []  # mnemonics of the last instructions of the current function
@@ -77,14 +71,11 @@ def test_exact_kernels_contain_no_fused_multiply_add(tmp_path):
     assert explained > 0   # the sqrt residuals are there: the scan did look inside the right functions
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-objdump")), reason="llvm-objdump not installed")
+@pytest.mark.skipif(not H.have_llvm_tools(), reason="llvm-objdump not installed")
 def test_streaming_kernels_address_lds_as_lds(tmp_path):
-    so = tmp_path / "libmuopdb_hip.so"
-    shutil.copy(L.LIB_PATH, so)
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", so.name], cwd=tmp_path, check=True, capture_output=True)
     flat, seen = {}, set()
-    for f in [f for f in os.listdir(tmp_path) if f.endswith("gfx950")]:
-        asm = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", f], cwd=tmp_path, check=True, capture_output=True, text=True).stdout
+    for f in H.extract_code_objects(L.LIB_PATH, tmp_path):
+        asm = H.disassemble(tmp_path, f)
         cur = None
         for line in asm.splitlines():
             m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
