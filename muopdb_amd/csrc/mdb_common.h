@@ -196,9 +196,9 @@ mdb_status mdb_fail(mdb_ctx* ctx, mdb_status st, const char* fmt, ...);
                             __FILE__, __LINE__);                                             \
     } while (0)
 
-#define MDB_TRY(expr)                    \
+#define MDB_TRY(...)                     \
     do {                                 \
-        mdb_status _s = (expr);          \
+        mdb_status _s = (__VA_ARGS__);   \
         if (_s != MDB_OK) return _s;     \
     } while (0)
 

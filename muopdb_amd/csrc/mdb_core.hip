@@ -4,6 +4,7 @@
 
 #include "mdb_device.hip.h"
 #include "mdb_kernels.h"
+#include "mdb_launch.hip.h"
 
 mdb_status mdb_fail(mdb_ctx* ctx, mdb_status st, const char* fmt, ...) {
     char buf[512];
@@ -400,14 +401,11 @@ extern "C" mdb_status mdb_lane_conforming_distance(mdb_ctx* ctx, const float* a,
     MDB_HIP(ctx, hipMemcpyAsync(da, a, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
     MDB_HIP(ctx, hipMemcpyAsync(db, b, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
     dim3 grid((unsigned)((n + 255) / 256));
-#define MDB_LC(METRIC)                                                                                                        \
-    do {                                                                                                                      \
-        if (lanes == 4) lane_conforming_kernel<METRIC, 4><<<grid, 256, 0, ctx->stream>>>((float*)da, (float*)db, n, d, (float*)dout);        \
-        else if (lanes == 8) lane_conforming_kernel<METRIC, 8><<<grid, 256, 0, ctx->stream>>>((float*)da, (float*)db, n, d, (float*)dout);   \
-        else lane_conforming_kernel<METRIC, 16><<<grid, 256, 0, ctx->stream>>>((float*)da, (float*)db, n, d, (float*)dout);                  \
-    } while (0)
-    if (metric == MDB_METRIC_L2) MDB_LC(MDB_METRIC_L2); else MDB_LC(MDB_METRIC_DOT);
-#undef MDB_LC
+    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+        return mdb_pick<4, 8, 16>(lanes, [&](auto LANES) {
+            return mdb_launch(ctx, lane_conforming_kernel<M(), LANES()>, grid, 256, 0, (float*)da, (float*)db, n, d, (float*)dout);
+        });
+    }));
     MDB_HIP(ctx, hipGetLastError());
     MDB_HIP(ctx, hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -10,6 +10,7 @@
 // (scalar loads).  Bound: HBM (N*d*4 bytes per pass); VALU = 3 ops per element per query.
 #include "mdb_device.hip.h"
 #include "mdb_kernels.h"
+#include "mdb_launch.hip.h"
 
 // ------------------------------------------------------------------------------------------ relayout
 __global__ __launch_bounds__(256) void rows_to_tiles_kernel(const float* __restrict__ rows, size_t n, int d, int d4,
@@ -680,13 +681,9 @@ static mdb_status launch_flat_scan(mdb_ctx* ctx, const TileView& ts, const DistP
     dim3 grid(nblk, (unsigned)(bpad / qt));
     size_t lds = BlockSelect<MDB_BLOCK>::lds_bytes(k) * qt;
     const float4* tiles = (const float4*)ts.data;
-#define MDB_LAUNCH(QT)                                                                                              \
-    flat_scan_kernel<METRIC, QT><<<grid, MDB_BLOCK, lds, ctx->stream>>>(tiles, ts.n, ts.ntiles, p, dq, qstride, k, \
-                                                                          partial, ctx->d_flags, gate)
-    if (qt == 4) MDB_LAUNCH(4);
-    else if (qt == 2) MDB_LAUNCH(2);
-    else MDB_LAUNCH(1);
-#undef MDB_LAUNCH
+    MDB_TRY(mdb_pick<4, 2, 1>(qt, [&](auto QT) {
+        return mdb_launch(ctx, flat_scan_kernel<METRIC, QT()>, grid, MDB_BLOCK, lds, tiles, ts.n, ts.ntiles, p, dq, qstride, k, partial, ctx->d_flags, gate);
+    }));
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
 }
@@ -737,28 +734,17 @@ mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const fl
         {
             ProfScope prof(ctx);
             ctx->prof_on = saved;
-#define MDB_SMALL_GO(METRIC, N)                                                                                                        \
-    do {                                                                                                                               \
-        if (fused) flat_small_block_kernel<METRIC, N><<<grid, FSB_BLOCK, 0, ctx->stream>>>(tiles, ts.n, ts.ntiles, dq, qstride, (int)k, (uint64_t*)partial, ctx->d_flags, fu); \
-        else if (sorted) flat_small_scan_kernel<METRIC, N, true><<<grid, MDB_BLOCK, 0, ctx->stream>>>(tiles, ts.n, ts.ntiles, dq, qstride, (int)k, (uint64_t*)partial, ctx->d_flags); \
-        else flat_small_scan_kernel<METRIC, N, false><<<grid, MDB_BLOCK, 0, ctx->stream>>>(tiles, ts.n, ts.ntiles, dq, qstride, (int)k, (uint64_t*)partial, ctx->d_flags);      \
-    } while (0)
-#define MDB_SMALL_N(METRIC)                        \
-    switch (p.n16) {                               \
-        case 1: MDB_SMALL_GO(METRIC, 1); break;    \
-        case 2: MDB_SMALL_GO(METRIC, 2); break;    \
-        case 3: MDB_SMALL_GO(METRIC, 3); break;    \
-        case 4: MDB_SMALL_GO(METRIC, 4); break;    \
-        case 5: MDB_SMALL_GO(METRIC, 5); break;    \
-        case 6: MDB_SMALL_GO(METRIC, 6); break;    \
-        case 7: MDB_SMALL_GO(METRIC, 7); break;    \
-        default: MDB_SMALL_GO(METRIC, 8); break;   \
-    }
-            if (metric == MDB_METRIC_L2) { MDB_SMALL_N(MDB_METRIC_L2) }
-            else if (metric == MDB_METRIC_L2SQ) { MDB_SMALL_N(MDB_METRIC_L2SQ) }
-            else { MDB_SMALL_N(MDB_METRIC_DOT) }
-#undef MDB_SMALL_N
-#undef MDB_SMALL_GO
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_L2SQ, MDB_METRIC_DOT>(metric, [&](auto M) {
+                return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
+                    if (fused)
+                        return mdb_launch(ctx, flat_small_block_kernel<M(), N()>, grid, FSB_BLOCK, 0, tiles, ts.n, ts.ntiles, dq, qstride, (int)k,
+                                          (uint64_t*)partial, ctx->d_flags, fu);
+                    return mdb_pick_bool(sorted, [&](auto SORTED) {
+                        return mdb_launch(ctx, flat_small_scan_kernel<M(), N(), SORTED()>, grid, MDB_BLOCK, 0, tiles, ts.n, ts.ntiles, dq, qstride, (int)k,
+                                          (uint64_t*)partial, ctx->d_flags);
+                    });
+                });
+            }));
             MDB_HIP(ctx, hipGetLastError());
         }
         if (!fused)

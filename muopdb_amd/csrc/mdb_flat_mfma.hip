@@ -24,6 +24,7 @@
 #include "mdb_common.h"
 #include "mdb_device.hip.h"
 #include "mdb_kernels.h"
+#include "mdb_launch.hip.h"
 
 #define MF_CAP 4096  // candidates refined per query (more => the batch falls back to the exact scan)
 
@@ -1500,34 +1501,24 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
         dim3 grids(nblk_s, (unsigned)groups);
         const size_t ldss = (size_t)QB * aux.nk * 2048 + BQ * 4 + BF_LBUF * 8 + 64;
         const float kappa_s = kappa + 8.0f * 5.9604645e-8f;
-#define BS_LAUNCH1(METRIC, QBT, NKT, X1T)                                                                                    \
-    do {                                                                                                                     \
-        if (ldss > 48 * 1024)                                                                                                \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)flat_bf16_filter_kernel<METRIC, QBT, NKT, true, false, X1T>,       \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldss));                       \
-        flat_bf16_filter_kernel<METRIC, QBT, NKT, true, false, X1T><<<grids, 256, ldss, ctx->stream>>>(                       \
-            aux.bhi.p, aux.blo.p, aux.xnorm.p, ts.n, snt32, aux.nk, dqc, qstride, crow, kappa_s, nullptr, (uint32_t*)umat, (uint32_t)ns, b, \
-            ctx->d_flags, aux.sample_stride, nullptr);                                                                                \
-    } while (0)
-#define BS_LAUNCH(METRIC, QBT, NKT) do { if (x1) BS_LAUNCH1(METRIC, QBT, NKT, true); else BS_LAUNCH1(METRIC, QBT, NKT, false); } while (0)
-#define BS_QB(METRIC, NKT)                                             \
-    do {                                                               \
-        if (QB == 8) BS_LAUNCH(METRIC, 8, NKT);                        \
-        else if (QB == 4) BS_LAUNCH(METRIC, 4, NKT);                   \
-        else if (QB == 2) BS_LAUNCH(METRIC, 2, NKT);                   \
-        else BS_LAUNCH(METRIC, 1, NKT);                                \
-    } while (0)
         if (xbound && smp_bf16) {
-#define BXB_LAUNCH(METRIC, QBT)                                                                                     \
-    flat_bf16x1_block_kernel<METRIC, QBT, true, false><<<gridxb, 256, BX_LDS, ctx->stream>>>(                        \
-        aux.bhi.p, aux.xnorm.p, ts.n, aux.nt32, dqc, qstride, bpadq, crow, kappa_s, nullptr, (uint32_t*)umat, (uint32_t)ns, b, ctx->d_flags, nullptr)
-            if (metric == MDB_METRIC_L2) BXB_LAUNCH(MDB_METRIC_L2, 2); else BXB_LAUNCH(MDB_METRIC_DOT, 2);
-#undef BXB_LAUNCH
-        } else if (metric == MDB_METRIC_L2) { if (aux.nk == 8) BS_QB(MDB_METRIC_L2, 8); else BS_QB(MDB_METRIC_L2, 0); }
-        else { if (aux.nk == 8) BS_QB(MDB_METRIC_DOT, 8); else BS_QB(MDB_METRIC_DOT, 0); }
-#undef BS_QB
-#undef BS_LAUNCH
-#undef BS_LAUNCH1
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+                return mdb_launch(ctx, flat_bf16x1_block_kernel<M(), 2, true, false>, gridxb, 256, BX_LDS, aux.bhi.p, aux.xnorm.p, ts.n, aux.nt32, dqc,
+                                  qstride, bpadq, crow, kappa_s, nullptr, (uint32_t*)umat, (uint32_t)ns, b, ctx->d_flags, nullptr);
+            }));
+        } else {
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+                return mdb_pick<8, 0>(aux.nk, [&](auto NK) {
+                    return mdb_pick<8, 4, 2, 1>(QB, [&](auto QBT) {
+                        return mdb_pick_bool(x1, [&](auto X1) {
+                            return mdb_launch(ctx, flat_bf16_filter_kernel<M(), QBT(), NK(), true, false, X1()>, grids, 256, ldss, aux.bhi.p, aux.blo.p,
+                                              aux.xnorm.p, ts.n, snt32, aux.nk, dqc, qstride, crow, kappa_s, nullptr, (uint32_t*)umat, (uint32_t)ns, b,
+                                              ctx->d_flags, aux.sample_stride, nullptr);
+                        });
+                    });
+                });
+            }));
+        }
         MDB_HIP(ctx, hipGetLastError());
         // (one WAVE per query at batch 4096 — no block barrier in the four radix passes, every query resident at once — measured the same: 27.4 / 27.4 us)
         if (b <= 256) sample_bound_kernel<1024><<<dim3((unsigned)b), 1024, 0, ctx->stream>>>(umat, (uint32_t)ns, (int)k, kappa, metric, crow, qnorm);
@@ -1547,27 +1538,6 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
             const unsigned nblk_b = (unsigned)std::max<size_t>(1, std::min<size_t>((aux.nt32 + 3) / 4, std::max<size_t>(1, 512 / groups)));
             dim3 gridb(nblk_b, (unsigned)groups);
             const size_t ldsb = (size_t)QB * aux.nk * 2048 + BQ * 4 + BF_LBUF * 8 + 64 + (qapx ? BF_LBUF * 4 : 0);
-#define BF_LAUNCH1(METRIC, QBT, NKT, APXT, X1T)                                                                      \
-    do {                                                                                                             \
-        if (ldsb > 48 * 1024)                                                                                        \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)flat_bf16_filter_kernel<METRIC, QBT, NKT, false, APXT, X1T>, \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));               \
-        flat_bf16_filter_kernel<METRIC, QBT, NKT, false, APXT, X1T><<<gridb, 256, ldsb, ctx->stream>>>(               \
-            aux.bhi.p, aux.blo.p, aux.xnorm.p, ts.n, aux.nt32, aux.nk, dqc, qstride, crow, kappa, qcnt, qids, qcap, b, ctx->d_flags, 0, qapx); \
-    } while (0)
-#define BF_LAUNCH0(METRIC, QBT, NKT, X1T)                  \
-    do {                                                   \
-        if (qapx) BF_LAUNCH1(METRIC, QBT, NKT, true, X1T); \
-        else BF_LAUNCH1(METRIC, QBT, NKT, false, X1T);     \
-    } while (0)
-#define BF_LAUNCH(METRIC, QBT, NKT) do { if (x1) BF_LAUNCH0(METRIC, QBT, NKT, true); else BF_LAUNCH0(METRIC, QBT, NKT, false); } while (0)
-#define BF_QB(METRIC, NKT)                                             \
-    do {                                                               \
-        if (QB == 8) BF_LAUNCH(METRIC, 8, NKT);                        \
-        else if (QB == 4) BF_LAUNCH(METRIC, 4, NKT);                   \
-        else if (QB == 2) BF_LAUNCH(METRIC, 2, NKT);                   \
-        else BF_LAUNCH(METRIC, 1, NKT);                                \
-    } while (0)
             if (xblock) {
                 // query blocks of 32 per wave (MDB_BF_BLOCK_QB): 1 -> 124 registers, FOUR blocks per CU; 2 -> 168, three; 4 -> 256 (39 spilled), two.
                 // Two pairs in three of a 64-probe coarse search hold a candidate, so the epilogue's candidate path is most of a wave's time
@@ -1581,36 +1551,40 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
                 const bool qb2 = qbo == 2, qb1 = qbo <= 1;
                 const size_t bq5 = qb1 ? 128 : (qb2 ? 256 : 512), g5 = (b + bq5 - 1) / bq5;
                 dim3 gridx((unsigned)std::max<size_t>(1, std::min<size_t>(aux.nt32, std::max<size_t>(1, (qb1 ? 1024 : (qb2 ? 768 : 512)) / g5))), (unsigned)g5);
-#define BX_LAUNCH(METRIC, APXT, QBT)                                                                                                 \
-    flat_bf16x1_block_kernel<METRIC, QBT, false, APXT><<<gridx, 256, BX_LDS, ctx->stream>>>(aux.bhi.p, aux.xnorm.p, ts.n, aux.nt32, dqc, qstride, bpadq, \
-                                                                                           crow, kappa, qcnt, qids, qcap, b, ctx->d_flags, qapx)
-#define BX_QB(METRIC, APXT) do { if (qb1) BX_LAUNCH(METRIC, APXT, 1); else if (qb2) BX_LAUNCH(METRIC, APXT, 2); else BX_LAUNCH(METRIC, APXT, 4); } while (0)
-                if (metric == MDB_METRIC_L2) { if (qapx) BX_QB(MDB_METRIC_L2, true); else BX_QB(MDB_METRIC_L2, false); }
-                else { if (qapx) BX_QB(MDB_METRIC_DOT, true); else BX_QB(MDB_METRIC_DOT, false); }
-#undef BX_QB
-#undef BX_LAUNCH
-            } else if (metric == MDB_METRIC_L2) { if (aux.nk == 8) BF_QB(MDB_METRIC_L2, 8); else BF_QB(MDB_METRIC_L2, 0); }
-            else { if (aux.nk == 8) BF_QB(MDB_METRIC_DOT, 8); else BF_QB(MDB_METRIC_DOT, 0); }
-#undef BF_QB
-#undef BF_LAUNCH
-#undef BF_LAUNCH0
-#undef BF_LAUNCH1
+                MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+                    return mdb_pick_bool(qapx != nullptr, [&](auto APX) {
+                        return mdb_pick<1, 2, 4>(qb1 ? 1 : qb2 ? 2 : 4, [&](auto QBT) {
+                            return mdb_launch(ctx, flat_bf16x1_block_kernel<M(), QBT(), false, APX()>, gridx, 256, BX_LDS, aux.bhi.p, aux.xnorm.p, ts.n,
+                                              aux.nt32, dqc, qstride, bpadq, crow, kappa, qcnt, qids, qcap, b, ctx->d_flags, qapx);
+                        });
+                    });
+                }));
+            } else {
+                MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+                    return mdb_pick<8, 0>(aux.nk, [&](auto NK) {
+                        return mdb_pick<8, 4, 2, 1>(QB, [&](auto QBT) {
+                            return mdb_pick_bool(x1, [&](auto X1) {
+                                return mdb_pick_bool(qapx != nullptr, [&](auto APX) {
+                                    return mdb_launch(ctx, flat_bf16_filter_kernel<M(), QBT(), NK(), false, APX(), X1()>, gridb, 256, ldsb, aux.bhi.p,
+                                                      aux.blo.p, aux.xnorm.p, ts.n, aux.nt32, aux.nk, dqc, qstride, crow, kappa, qcnt, qids, qcap, b,
+                                                      ctx->d_flags, 0, qapx);
+                                });
+                            });
+                        });
+                    });
+                }));
+            }
             MDB_HIP(ctx, hipGetLastError());
         } else {
         unsigned nblk = (unsigned)std::min<size_t>((ts.ntiles + 3) / 4, groups >= 4 ? 256 : 512);
         dim3 grid(nblk, (unsigned)groups);
         size_t lds = (size_t)((ts.d4 + MF_CH - 1) / MF_CH * MF_CH) * 4 * (BQ + 1) * 4 + (BQ + 2) * 4 + MF_LBUF * 8 + 16;
-#define MF_LAUNCH(METRIC, QBT)                                                                                       \
-    do {                                                                                                             \
-        if (lds > 48 * 1024)                                                                                         \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)flat_mfma_filter_kernel<METRIC, QBT>,                      \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                \
-        flat_mfma_filter_kernel<METRIC, QBT><<<grid, 256, lds, ctx->stream>>>(ftiles, ts.n, ts.ntiles, ts.d4, dqc, qstride, crow,    \
-                                                                              kappa, qcnt, qids, qcap, b, ctx->d_flags);                           \
-    } while (0)
-        if (metric == MDB_METRIC_L2) { if (QB == 2) MF_LAUNCH(MDB_METRIC_L2, 2); else MF_LAUNCH(MDB_METRIC_L2, 1); }
-        else { if (QB == 2) MF_LAUNCH(MDB_METRIC_DOT, 2); else MF_LAUNCH(MDB_METRIC_DOT, 1); }
-#undef MF_LAUNCH
+        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+            return mdb_pick<2, 1>(QB, [&](auto QBT) {
+                return mdb_launch(ctx, flat_mfma_filter_kernel<M(), QBT()>, grid, 256, lds, ftiles, ts.n, ts.ntiles, ts.d4, dqc, qstride, crow, kappa, qcnt,
+                                  qids, qcap, b, ctx->d_flags);
+            });
+        }));
         MDB_HIP(ctx, hipGetLastError());
         }
     }
@@ -1625,13 +1599,13 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
         UnpackOut up = unpack ? *unpack : UnpackOut{};
         if (aux.d_ovf_host) { up.word_src = ovf; up.word_dst = aux.d_ovf_host; }
         const bool n8 = metric == MDB_METRIC_L2 && ts.d == 128;
-#define RG_LAUNCH(METRIC, N16C)                                                                                                        \
-    flat_refine_group_kernel<METRIC, N16C><<<dim3((unsigned)b), 256, ldsg, ctx->stream>>>(aux.rows.p, p, dq, qstride, qcnt, qids, qcap, (int)k, \
-                                                                                         d_keys, d_counts, ovf, ctx->d_flags, ts.n, up, qapx, \
-                                                                                         aux.xnorm.p, qnorm, kappa_s, rg_cap, rg_surv)
-        if (metric == MDB_METRIC_L2) { if (n8) RG_LAUNCH(MDB_METRIC_L2, 8); else RG_LAUNCH(MDB_METRIC_L2, 0); }
-        else RG_LAUNCH(MDB_METRIC_DOT, 0);
-#undef RG_LAUNCH
+        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+            return mdb_pick<8, 0>(n8 ? 8 : 0, [&](auto N8) {
+                constexpr int N16C = M() == MDB_METRIC_L2 ? N8() : 0;   // (n8 is L2 only)
+                return mdb_launch(ctx, flat_refine_group_kernel<M(), N16C>, dim3((unsigned)b), 256, ldsg, aux.rows.p, p, dq, qstride, qcnt, qids, qcap,
+                                  (int)k, d_keys, d_counts, ovf, ctx->d_flags, ts.n, up, qapx, aux.xnorm.p, qnorm, kappa_s, rg_cap, rg_surv);
+            });
+        }));
         MDB_HIP(ctx, hipGetLastError());
         if (!aux.d_ovf_host) MDB_HIP(ctx, hipMemcpyAsync(aux.h_ovf, ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
         return MDB_OK;
@@ -1647,18 +1621,14 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
     MDB_TRY(mdb_scratch(ctx, 10, b * (size_t)rs * std::max<size_t>(k, 1) * 8, (void**)&rpart));
     const bool rows = aux.rows.p != nullptr;
     const float4* rsrc = rows ? (const float4*)aux.rows.p : (const float4*)ts.data;
-#define RF_LAUNCH(METRIC, ROWS)                                                                                                \
-    do {                                                                                                                       \
-        if (wave_slices)                                                                                                       \
-            flat_refine_kernel<METRIC, ROWS, 64><<<dim3(rs, (unsigned)b), 64, sel_lds, ctx->stream>>>(rsrc, p, dq, qstride, qcnt, qids, qcap, \
-                                                                                                   (int)k, rpart, ovf, ctx->d_flags, ts.n);  \
-        else                                                                                                                   \
-            flat_refine_kernel<METRIC, ROWS, MDB_BLOCK><<<dim3(rs, (unsigned)b), MDB_BLOCK, sel_lds, ctx->stream>>>(                          \
-                rsrc, p, dq, qstride, qcnt, qids, qcap, (int)k, rpart, ovf, ctx->d_flags, ts.n);                                              \
-    } while (0)
-    if (metric == MDB_METRIC_L2) { if (rows) RF_LAUNCH(MDB_METRIC_L2, true); else RF_LAUNCH(MDB_METRIC_L2, false); }
-    else { if (rows) RF_LAUNCH(MDB_METRIC_DOT, true); else RF_LAUNCH(MDB_METRIC_DOT, false); }
-#undef RF_LAUNCH
+    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+        return mdb_pick_bool(rows, [&](auto ROWS) {
+            return mdb_pick<64, MDB_BLOCK>(wave_slices ? 64 : MDB_BLOCK, [&](auto BLK) {
+                return mdb_launch(ctx, flat_refine_kernel<M(), ROWS(), BLK()>, dim3(rs, (unsigned)b), BLK(), sel_lds, rsrc, p, dq, qstride, qcnt, qids,
+                                  qcap, (int)k, rpart, ovf, ctx->d_flags, ts.n);
+            });
+        });
+    }));
     MDB_HIP(ctx, hipGetLastError());
     // the merge of the slices is the step's LAST kernel: it also writes the caller's rows (unpack) and hands the overflow count to
     // the host (pinned word, read one call late) — no unpack launch, no counts copy, no device-to-host copy, and no gated exact

@@ -26,6 +26,7 @@
 #include "mdb_hnsw.h"
 #include "mdb_hnsw_dev.hip.h"
 #include "mdb_kernels.h"
+#include "mdb_launch.hip.h"
 
 #define HNSW_BLOCK 256
 #define HNSW_MAX_STRIDE 256
@@ -1778,53 +1779,8 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
         a.vis_global = (uint32_t*)vg;
     }
     ProfScope prof(ctx, 2);
-#define MDB_HNSW_LAUNCH4(METRIC, VL, NF)                                                                                    \
-    do {                                                                                                                   \
-        if (lds > 48 * 1024)                                                                                               \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_search_kernel<METRIC, VL, NF>,                              \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                       \
-        hnsw_search_kernel<METRIC, VL, NF><<<dim3((unsigned)b), HNSW_BLOCK, lds, ctx->stream>>>(a);                        \
-    } while (0)
     // specialised distance when the whole vector is 16-lane chunks (d = 128 / 768: the configs' dims)
     const int nf = (kind != MDB_QUANT_PQ && a.p.n8 == 0 && a.p.n4 == 0 && a.p.ntail == 0 && !ctx->opt.hnsw_generic_dist) ? a.p.n16 : 0;
-#define MDB_BEAM_LAUNCH(METRIC, VL, NF, R64)                                                                                   \
-    do {                                                                                                                    \
-        if (lds > 48 * 1024)                                                                                                \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_beam_kernel<METRIC, VL, NF, R64>,                             \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hnsw_beam_kernel<METRIC, VL, NF, R64><<<dim3((unsigned)b), HNSW_BLOCK, lds, ctx->stream>>>(a); \
-    } while (0)
-#define MDB_BEAM_LAUNCH_L0N(METRIC, VL, NF, NBV)                                                                            \
-    do {                                                                                                                    \
-        if (lds > 48 * 1024)                                                                                                \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_beam_kernel<METRIC, VL, NF, true, true, NBV>,         \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hnsw_beam_kernel<METRIC, VL, NF, true, true, NBV><<<dim3((unsigned)b), HNSW_BLOCK, lds, ctx->stream>>>(a);   \
-    } while (0)
-#define MDB_BEAM_LAUNCH_L0(METRIC, VL, NF)                                                                              \
-    do {                                                                                                                    \
-        if (hnsw_beam_nb4(ctx, ef)) MDB_BEAM_LAUNCH_L0N(METRIC, VL, NF, 4);                                                 \
-        else if (ef <= 256) MDB_BEAM_LAUNCH_L0N(METRIC, VL, NF, 5);                                                         \
-        else MDB_BEAM_LAUNCH_L0N(METRIC, VL, NF, 8);                                                                        \
-    } while (0)
-#define MDB_HNSW_LAUNCH(METRIC, VL)                                                                              \
-    do {                                                                                                           \
-        if (table) {                                                                                               \
-            if (nf == 8) MDB_BEAM_LAUNCH_L0(METRIC, VL, 8);                                                 \
-            else if (nf == 48) MDB_BEAM_LAUNCH_L0(METRIC, VL, 48);                                          \
-            else MDB_BEAM_LAUNCH_L0(METRIC, VL, 0);                                                         \
-        } else if (beam && row64) {                                                                                \
-            if (nf == 8) MDB_BEAM_LAUNCH(METRIC, VL, 8, true);                                              \
-            else if (nf == 48) MDB_BEAM_LAUNCH(METRIC, VL, 48, true);                                       \
-            else MDB_BEAM_LAUNCH(METRIC, VL, 0, true);                                                      \
-        } else if (beam) {                                                                                         \
-            if (nf == 8) MDB_BEAM_LAUNCH(METRIC, VL, 8, false);                                             \
-            else if (nf == 48) MDB_BEAM_LAUNCH(METRIC, VL, 48, false);                                      \
-            else MDB_BEAM_LAUNCH(METRIC, VL, 0, false);                                                     \
-        } else if (nf == 8) MDB_HNSW_LAUNCH4(METRIC, VL, 8);                                                       \
-        else if (nf == 48) MDB_HNSW_LAUNCH4(METRIC, VL, 48);                                                       \
-        else MDB_HNSW_LAUNCH4(METRIC, VL, 0);                                                                      \
-    } while (0)
     // graphs no larger than ef (SPANN centroid graphs): frontier-parallel closure, see hnsw_closure_kernel
     if (max_n <= ef && max_n <= 4096 && !ctx->opt.hnsw_no_closure) {
         if (zero_counters) { ctx->counters_clean = false; MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 128, ctx->stream)); }
@@ -1856,28 +1812,13 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
                 }
             }
         }
-#define MDB_CLOSURE_LAUNCH(METRIC, NF, CB)                                                                                    \
-    do {                                                                                                                    \
-        if (clds > 48 * 1024)                                                                                               \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_closure_kernel<METRIC, NF, CB>,                              \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));                       \
-        hnsw_closure_kernel<METRIC, NF, CB><<<dim3((unsigned)b), CB, clds, ctx->stream>>>(a, wcap, stg, cfk);                        \
-    } while (0)
-#define MDB_CLOSURE_LAUNCH_M(METRIC)                                 \
-    do {                                                             \
-        if (big) {                                                   \
-            if (nf == 8) MDB_CLOSURE_LAUNCH(METRIC, 8, 1024);        \
-            else if (nf == 48) MDB_CLOSURE_LAUNCH(METRIC, 48, 1024); \
-            else MDB_CLOSURE_LAUNCH(METRIC, 0, 1024);                \
-        } else {                                                     \
-            if (nf == 8) MDB_CLOSURE_LAUNCH(METRIC, 8, 256);         \
-            else if (nf == 48) MDB_CLOSURE_LAUNCH(METRIC, 48, 256);  \
-            else MDB_CLOSURE_LAUNCH(METRIC, 0, 256);                 \
-        }                                                            \
-    } while (0)
-        if (metric == MDB_METRIC_L2) MDB_CLOSURE_LAUNCH_M(MDB_METRIC_L2); else MDB_CLOSURE_LAUNCH_M(MDB_METRIC_DOT);
-#undef MDB_CLOSURE_LAUNCH_M
-#undef MDB_CLOSURE_LAUNCH
+        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+            return mdb_pick<1024, 256>(big ? 1024 : 256, [&](auto CB) {
+                return mdb_pick<8, 48, 0>(nf, [&](auto NF) {
+                    return mdb_launch(ctx, hnsw_closure_kernel<M(), NF(), CB()>, dim3((unsigned)b), CB(), clds, a, wcap, stg, cfk);
+                });
+            });
+        }));
         MDB_HIP(ctx, hipGetLastError());
         return MDB_OK;
     }
@@ -1917,16 +1858,22 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
         }
     }
     if (zero_counters) { ctx->counters_clean = false; MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 128, ctx->stream)); }
-    if (metric == MDB_METRIC_L2) {
-        if (vis_lds) MDB_HNSW_LAUNCH(MDB_METRIC_L2, true); else MDB_HNSW_LAUNCH(MDB_METRIC_L2, false);
-    } else {
-        if (vis_lds) MDB_HNSW_LAUNCH(MDB_METRIC_DOT, true); else MDB_HNSW_LAUNCH(MDB_METRIC_DOT, false);
-    }
-#undef MDB_BEAM_LAUNCH
-#undef MDB_BEAM_LAUNCH_L0
-#undef MDB_BEAM_LAUNCH_L0N
-#undef MDB_HNSW_LAUNCH4
-#undef MDB_HNSW_LAUNCH
+    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+        return mdb_pick_bool(vis_lds, [&](auto VL) {
+            return mdb_pick<8, 48, 0>(nf, [&](auto NF) {
+                const dim3 grid((unsigned)b);
+                if (table)   // layer 0 behind the table pass: the beam's registers as in upper_launch_bottom
+                    return mdb_pick<4, 5, 8>(hnsw_beam_nb4(ctx, ef) ? 4 : ef <= 256 ? 5 : 8, [&](auto NB) {
+                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), true, true, NB()>, grid, HNSW_BLOCK, lds, a);
+                    });
+                if (beam)
+                    return mdb_pick_bool(row64, [&](auto R64) {
+                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), R64()>, grid, HNSW_BLOCK, lds, a);
+                    });
+                return mdb_launch(ctx, hnsw_search_kernel<M(), VL(), NF()>, grid, HNSW_BLOCK, lds, a);
+            });
+        });
+    }));
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
 }

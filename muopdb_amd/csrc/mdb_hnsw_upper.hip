@@ -18,6 +18,7 @@
 #include "mdb_hnsw.h"
 #include "mdb_hnsw_dev.hip.h"
 #include "mdb_kernels.h"
+#include "mdb_launch.hip.h"
 
 // ------------------------------------------------------------------------------------------ table
 // grid (tiles, query groups of QT); one wave = one tile of 64 upper points, thread = point
@@ -213,62 +214,44 @@ mdb_status hnsw_upper_table(mdb_ctx* ctx, const HnswUpper& up, int metric, const
     const float4* tiles = (const float4*)up.tiles.data.p;
     if (up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 && (long long)b >= ctx->opt.hnsw_table64_min_b) {
         const unsigned gx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), gy = (unsigned)((b + 63) / 64);
-#define MDB_UT64_GO(METRIC, N)                                                                               \
-    hnsw_upper_table64_kernel<METRIC, N><<<dim3(gx, gy), 256, 0, ctx->stream>>>(up.rows_nat.p, up.nu, d_q, qstride, (uint32_t)b, d_table, nu_pad, zero16)
-#define MDB_UT64_LAUNCH(METRIC)                            \
-    do {                                                   \
-        switch (p.n16) {                                   \
-            case 1: MDB_UT64_GO(METRIC, 1); break;         \
-            case 2: MDB_UT64_GO(METRIC, 2); break;         \
-            case 3: MDB_UT64_GO(METRIC, 3); break;         \
-            case 4: MDB_UT64_GO(METRIC, 4); break;         \
-            case 5: MDB_UT64_GO(METRIC, 5); break;         \
-            case 6: MDB_UT64_GO(METRIC, 6); break;         \
-            case 7: MDB_UT64_GO(METRIC, 7); break;         \
-            default: MDB_UT64_GO(METRIC, 8); break;        \
-        }                                                  \
-    } while (0)
-        if (metric == MDB_METRIC_L2) MDB_UT64_LAUNCH(MDB_METRIC_L2); else MDB_UT64_LAUNCH(MDB_METRIC_DOT);
-#undef MDB_UT64_LAUNCH
-#undef MDB_UT64_GO
+        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+            return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
+                return mdb_launch(ctx, hnsw_upper_table64_kernel<M(), N()>, dim3(gx, gy), 256, 0, up.rows_nat.p, up.nu, d_q, qstride, (uint32_t)b, d_table,
+                                  nu_pad, zero16);
+            });
+        }));
         MDB_HIP(ctx, hipGetLastError());
         return MDB_OK;
     }
     if (p.n16 > 0 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0) {
         const unsigned gx = (unsigned)((up.tiles.ntiles + 3) / 4);
         const int qf = ctx->opt.hnsw_table_qt == 8 ? 8 : ctx->opt.hnsw_table_qt == 2 ? 2 : 4;
-#define MDB_UT16_GO(METRIC, QF, first, groups)                                                                                     \
-    hnsw_upper_table16_kernel<METRIC, QF><<<dim3(gx, (groups)), 256, 0, ctx->stream>>>(                                            \
-        tiles, up.nu, (uint32_t)up.tiles.ntiles, p.n16, d_q, qstride, (first), d_table, nu_pad, (first) == 0u ? zero16 : nullptr)
-#define MDB_UT16_LAUNCH(METRIC)                                                                                                   \
-    do {                                                                                                                          \
-        const uint32_t full = (uint32_t)(b / qf), rest = (uint32_t)(b % qf);                                                      \
-        if (full) {                                                                                                               \
-            if (qf == 8) MDB_UT16_GO(METRIC, 8, 0u, full);                                                                        \
-            else if (qf == 4) MDB_UT16_GO(METRIC, 4, 0u, full);                                                                   \
-            else MDB_UT16_GO(METRIC, 2, 0u, full);                                                                                \
-        }                                                                                                                         \
-        if (rest) MDB_UT16_GO(METRIC, 1, full * qf, rest);                                                                        \
-    } while (0)
-        if (metric == MDB_METRIC_L2) MDB_UT16_LAUNCH(MDB_METRIC_L2); else MDB_UT16_LAUNCH(MDB_METRIC_DOT);
-#undef MDB_UT16_LAUNCH
-#undef MDB_UT16_GO
+        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+            const uint32_t full = (uint32_t)(b / qf), rest = (uint32_t)(b % qf);
+            if (full)
+                MDB_TRY(mdb_pick<8, 4, 2>(qf, [&](auto QF) {
+                    return mdb_launch(ctx, hnsw_upper_table16_kernel<M(), QF()>, dim3(gx, full), 256, 0, tiles, up.nu, (uint32_t)up.tiles.ntiles, p.n16,
+                                      d_q, qstride, 0u, d_table, nu_pad, zero16);
+                }));
+            if (rest)
+                MDB_TRY(mdb_launch(ctx, hnsw_upper_table16_kernel<M(), 1>, dim3(gx, rest), 256, 0, tiles, up.nu, (uint32_t)up.tiles.ntiles, p.n16, d_q,
+                                   qstride, full * qf, d_table, nu_pad, full * qf == 0u ? zero16 : nullptr));
+            return MDB_OK;
+        }));
         MDB_HIP(ctx, hipGetLastError());
         return MDB_OK;
     }
     constexpr int QT = 2;   // any dimension: the cascade of exact_sums
     const uint32_t full = (uint32_t)(b / QT), rest = (uint32_t)(b % QT);
-#define MDB_UT_LAUNCH(METRIC)                                                                                                     \
-    do {                                                                                                                          \
-        if (full)                                                                                                                 \
-            hnsw_upper_table_kernel<METRIC, QT><<<dim3((unsigned)up.tiles.ntiles, full), 64, 0, ctx->stream>>>(                    \
-                tiles, up.nu, p, d_q, qstride, 0u, d_table, nu_pad, zero16);                                                              \
-        if (rest)                                                                                                                 \
-            hnsw_upper_table_kernel<METRIC, 1><<<dim3((unsigned)up.tiles.ntiles, rest), 64, 0, ctx->stream>>>(                     \
-                tiles, up.nu, p, d_q, qstride, full * QT, d_table, nu_pad, full ? nullptr : zero16);                                                       \
-    } while (0)
-    if (metric == MDB_METRIC_L2) MDB_UT_LAUNCH(MDB_METRIC_L2); else MDB_UT_LAUNCH(MDB_METRIC_DOT);
-#undef MDB_UT_LAUNCH
+    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+        if (full)
+            MDB_TRY(mdb_launch(ctx, hnsw_upper_table_kernel<M(), QT>, dim3((unsigned)up.tiles.ntiles, full), 64, 0, tiles, up.nu, p, d_q, qstride, 0u,
+                               d_table, nu_pad, zero16));
+        if (rest)
+            MDB_TRY(mdb_launch(ctx, hnsw_upper_table_kernel<M(), 1>, dim3((unsigned)up.tiles.ntiles, rest), 64, 0, tiles, up.nu, p, d_q, qstride,
+                               full * QT, d_table, nu_pad, full ? nullptr : zero16));
+        return MDB_OK;
+    }));
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
 }
@@ -846,16 +829,9 @@ static mdb_status upper_launch_bottom(mdb_ctx* ctx, const HnswUpper& up, const u
     {
         const size_t rlds = rk_lds_bytes(out.words, a.nu_pad, RK_BLOCK, 0);
         if ((ctx->opt.hnsw_rank & 1) && a.nu <= RK_MAX_POINTS && a.nu_pad <= RK_MAX_POINTS && rlds <= 160 * 1024 - 512) {
-#define MDB_RK_GO(NWV)                                                                                                                \
-    do {                                                                                                                              \
-        if (rlds > 48 * 1024)                                                                                                         \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_upper_rank_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); \
-        hnsw_upper_rank_kernel<NWV><<<dim3((unsigned)b), RK_BLOCK, rlds, ctx->stream>>>(a);                                           \
-    } while (0)
-            if (a.nu_pad <= 2048) MDB_RK_GO(1);
-            else if (a.nu_pad <= 8192) MDB_RK_GO(4);
-            else MDB_RK_GO(16);
-#undef MDB_RK_GO
+            MDB_TRY(mdb_pick<1, 4, 16>(a.nu_pad <= 2048 ? 1 : a.nu_pad <= 8192 ? 4 : 16, [&](auto NW) {
+                return mdb_launch(ctx, hnsw_upper_rank_kernel<NW()>, dim3((unsigned)b), RK_BLOCK, rlds, a);
+            }));
             MDB_HIP(ctx, hipGetLastError());
             return MDB_OK;
         }
@@ -863,18 +839,11 @@ static mdb_status upper_launch_bottom(mdb_ctx* ctx, const HnswUpper& up, const u
     const size_t lds_base = UP_LDS_VIS + (size_t)out.words * 4;
     const bool tlds = lds_base + (size_t)a.nu_pad * 4 <= 160 * 1024 - 512 && !ctx->opt.hnsw_table_no_lds;
     const size_t lds = lds_base + (tlds ? (size_t)a.nu_pad * 4 : 0);
-#define MDB_UPK_GO(TL, NBV)                                                                                                           \
-    do {                                                                                                                              \
-        if (lds > 48 * 1024)                                                                                                          \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_upper_kernel<TL, NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hnsw_upper_kernel<TL, NBV><<<dim3((unsigned)b), UP_BLOCK, lds, ctx->stream>>>(a);                                            \
-    } while (0)
     // registers of 64 beam slots: every count, selection and push of a step loops over them — four when ef leaves them enough slack
     // (a compaction every ~slack accepted neighbours costs less than a fifth register in every step), five up to 256, eight beyond
-    if (hnsw_beam_nb4(ctx, ef)) { if (tlds) MDB_UPK_GO(true, 4); else MDB_UPK_GO(false, 4); }
-    else if (ef <= 256) { if (tlds) MDB_UPK_GO(true, 5); else MDB_UPK_GO(false, 5); }
-    else { if (tlds) MDB_UPK_GO(true, 8); else MDB_UPK_GO(false, 8); }
-#undef MDB_UPK_GO
+    MDB_TRY(mdb_pick<4, 5, 8>(hnsw_beam_nb4(ctx, ef) ? 4 : ef <= 256 ? 5 : 8, [&](auto NB) {
+        return mdb_pick_bool(tlds, [&](auto TL) { return mdb_launch(ctx, hnsw_upper_kernel<TL(), NB()>, dim3((unsigned)b), UP_BLOCK, lds, a); });
+    }));
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
 }
@@ -919,46 +888,19 @@ mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const D
     const unsigned tgx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), tgy = (unsigned)((b + 63) / 64);
     const unsigned grid = (unsigned)b + tgx * tgy;
     const bool nb4 = hnsw_beam_nb4(ctx, ef);
-#define MDB_TOP_GO1(METRIC, N, NBV)                                                                                                    \
-    do {                                                                                                                               \
-        if (lds_top > 48 * 1024)                                                                                                       \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_upper_top_kernel<METRIC, N, NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                             (int)lds_top));                                                                           \
-        hnsw_upper_top_kernel<METRIC, N, NBV><<<dim3(grid), 256, lds_top, ctx->stream>>>(a, (uint32_t)b, up.rows_nat.p, up.nu, d_table, nu_pad, \
-                                                                                         tgx, zero16);                                \
-    } while (0)
-#define MDB_TOP_RK1(METRIC, N, NWV)                                                                                                    \
-    do {                                                                                                                               \
-        if (lds_top_rank > 48 * 1024)                                                                                                  \
-            MDB_HIP(ctx, hipFuncSetAttribute((const void*)hnsw_upper_top_rank_kernel<METRIC, N, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                             (int)lds_top_rank));                                                                      \
-        hnsw_upper_top_rank_kernel<METRIC, N, NWV><<<dim3(grid), 256, lds_top_rank, ctx->stream>>>(a, (uint32_t)b, up.rows_nat.p, up.nu, d_table, \
-                                                                                                    nu_pad, tgx, zero16);              \
-    } while (0)
-#define MDB_TOP_GO(METRIC, N)                                                                  \
-    do {                                                                                       \
-        if (top_rank) { if (nu2_pad <= 2048) MDB_TOP_RK1(METRIC, N, 1); else MDB_TOP_RK1(METRIC, N, 4); } \
-        else if (nb4) MDB_TOP_GO1(METRIC, N, 4);                                               \
-        else MDB_TOP_GO1(METRIC, N, 5);                                                        \
-    } while (0)
-#define MDB_TOP_LAUNCH(METRIC)                           \
-    do {                                                 \
-        switch (p.n16) {                                 \
-            case 1: MDB_TOP_GO(METRIC, 1); break;        \
-            case 2: MDB_TOP_GO(METRIC, 2); break;        \
-            case 3: MDB_TOP_GO(METRIC, 3); break;        \
-            case 4: MDB_TOP_GO(METRIC, 4); break;        \
-            case 5: MDB_TOP_GO(METRIC, 5); break;        \
-            case 6: MDB_TOP_GO(METRIC, 6); break;        \
-            case 7: MDB_TOP_GO(METRIC, 7); break;        \
-            default: MDB_TOP_GO(METRIC, 8); break;       \
-        }                                                \
-    } while (0)
-    if (metric == MDB_METRIC_L2) MDB_TOP_LAUNCH(MDB_METRIC_L2); else MDB_TOP_LAUNCH(MDB_METRIC_DOT);
-#undef MDB_TOP_LAUNCH
-#undef MDB_TOP_GO
-#undef MDB_TOP_RK1
-#undef MDB_TOP_GO1
+    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+        return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
+            if (top_rank)
+                return mdb_pick<1, 4>(nu2_pad <= 2048 ? 1 : 4, [&](auto NW) {
+                    return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), NW()>, dim3(grid), 256, lds_top_rank, a, (uint32_t)b, up.rows_nat.p, up.nu,
+                                      d_table, nu_pad, tgx, zero16);
+                });
+            return mdb_pick<4, 5>(nb4 ? 4 : 5, [&](auto NB) {
+                return mdb_launch(ctx, hnsw_upper_top_kernel<M(), N(), NB()>, dim3(grid), 256, lds_top, a, (uint32_t)b, up.rows_nat.p, up.nu, d_table,
+                                  nu_pad, tgx, zero16);
+            });
+        });
+    }));
     MDB_HIP(ctx, hipGetLastError());
     return upper_launch_bottom(ctx, up, d_table, b, ef, out, 1, st_ep, st_ovf, st_vis, st_cnt);
 }

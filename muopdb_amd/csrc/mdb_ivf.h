@@ -141,4 +141,9 @@ struct IvfSet {
                             float* d_score, uint32_t* d_counts_out, uint8_t* d_found_out);
     // algorithmic bytes per scored vector
     size_t bytes_per_scored() const { return (kind == MDB_QUANT_PQ ? (size_t)pq.m : (size_t)num_features * 4) + 4; }
+
+private:
+    // what a scan reads of the planner's filter and the tombstones: validated against the batch and chosen HERE for scan and search_fused
+    struct ScanMasks { const uint32_t* allow; uint32_t allow_stride, allow_mask, no_masks; };
+    mdb_status scan_masks(const ScanFilter* filter, size_t b, ScanMasks* out) const;
 };

@@ -709,21 +709,15 @@ static mdb_status cm_launch(mdb_ctx* ctx, const CoarseMfma& cm, const float* d_q
         a.dbg = (unsigned long long*)dbg;
     }
     const dim3 grid(a.nblocks_coarse + qblocks);
-#define MDB_CM_Q(NKT, JT, TWT) ivf_coarse_mfma_kernel<NKT, JT, TWT><<<grid, CM_BLOCK, 0, ctx->stream>>>(a)
-#define MDB_CM_T(NKT, JT) do { if (sh.TW == 2) MDB_CM_Q(NKT, JT, 2); else MDB_CM_Q(NKT, JT, 4); } while (0)
-#define MDB_CM_J(NKT) do { if (sh.J == 1) MDB_CM_T(NKT, 1); else if (sh.J == 2) MDB_CM_T(NKT, 2); else if (sh.J == 4) MDB_CM_T(NKT, 4); else MDB_CM_T(NKT, 8); } while (0)
-    switch (cm.nk) {
-        case 4: MDB_CM_J(4); break;
-        case 6: MDB_CM_J(6); break;
-        case 8: MDB_CM_J(8); break;
-        case 12: MDB_CM_J(12); break;
-        case 16: MDB_CM_J(16); break;
-        default: return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "coarse matrix-core search: dimension %d", cm.nk * 16);
-    }
-    if (ctx->opt.cm_dbg >= 2 && cm.nk == 8) MDB_CM_J(8);   // the same launch again: its stamps are those of a warm instruction cache / L2
-#undef MDB_CM_J
-#undef MDB_CM_T
-#undef MDB_CM_Q
+    auto launch = [&] {
+        return mdb_pick_or<4, 6, 8, 12, 16>(cm.nk, [&](auto NK) {
+            return mdb_pick<1, 2, 4, 8>(sh.J, [&](auto J) {
+                return mdb_pick<2, 4>(sh.TW, [&](auto TW) { return mdb_launch(ctx, ivf_coarse_mfma_kernel<NK(), J(), TW()>, grid, CM_BLOCK, 0, a); });
+            });
+        }, [&] { return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "coarse matrix-core search: dimension %d", cm.nk * 16); });
+    };
+    MDB_TRY(launch());
+    if (ctx->opt.cm_dbg >= 2 && cm.nk == 8) MDB_TRY(launch());   // the same launch again: its stamps are those of a warm instruction cache / L2
     MDB_HIP(ctx, hipGetLastError());
     if (ctx->opt.cm_dbg) {   // candidates per query (synchronises)
         std::vector<uint32_t> h(b * sh.S);

@@ -20,6 +20,7 @@
 #include "mdb_hnsw.h"
 #include "mdb_ivf.h"
 #include "mdb_kernels.h"
+#include "mdb_launch.hip.h"
 
 struct SpannSet {
     mdb_ctx* ctx = nullptr;
@@ -321,10 +322,8 @@ static mdb_status merge_shards_launch(mdb_ctx* ctx, const char* docs, size_t ds,
     }
     size_t lds = world * k * 20 + (world + 1) * 4 + 16;
     if (lds > 150 * 1024) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "world*k=%zu rows exceed the on-chip merge capacity", world * k);
-    if (lds > 48 * 1024)
-        MDB_HIP(ctx, hipFuncSetAttribute((const void*)merge_shards_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    merge_shards_kernel<<<dim3((unsigned)b), 256, lds, ctx->stream>>>(docs, ds, scores, ss, counts, cs, (int)world, b, (int)k, doc_ids_out,
-                                                                     scores_out, counts_out);
+    MDB_TRY(mdb_launch(ctx, merge_shards_kernel, dim3((unsigned)b), 256, lds, docs, ds, scores, ss, counts, cs, (int)world, b, (int)k, doc_ids_out,
+                       scores_out, counts_out));
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
 }
