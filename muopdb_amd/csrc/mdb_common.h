@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/muopdb_hip.h"
+#include "mdb_arena.h"
 
 #define MDB_WAVE 64
 #define MDB_TILE 64          // vectors per tile of the list-contiguous SoA layout (one per lane)
@@ -124,17 +125,15 @@ struct mdb_ctx {
     unsigned long long* h_counters = nullptr;
     bool dev_counters = true;      // false: the last call used no device counters (flat scans): mdb_get_stats reports zeros, no memset launch
     uint64_t stat_bytes_per_eval = 0, stat_bytes_per_scored = 0, stat_fixed_bytes = 0;
-    // growable device scratch (never shrinks; no allocation in steady state)
-    void* scratch[16] = {nullptr};
-    size_t scratch_cap[16] = {0};
+    // device scratch of the API call in progress (mdb_scratch; MDB_ENTER begins a call): no allocation in steady state
+    mdb_arena arena;
     // optional HIP-event timing of the dominant kernel of each search call (mdb_set_profiling)
     bool prof_on = false;
     int prof_mask = 3;   // MDB_PROF_SCAN | MDB_PROF_HNSW: which kernel classes are bracketed
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
     size_t prof_used = 0;
-    // pinned host staging for MDB_MEM_HOST calls: [0] inputs, [1] outputs.  Pageable hipMemcpyAsync costs ~0.2 ms a call
+    // pinned host staging for MDB_MEM_HOST calls, one buffer per mdb_pin role.  Pageable hipMemcpyAsync costs ~0.2 ms a call
     // on this stack; user buffer <-> pinned is a CPU memcpy, pinned <-> device a true async copy.
-    // [2] per-call filter bitmaps, [3] small auxiliary inputs (per-query user indices, probe lists)
     void* pinned[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t pinned_cap[4] = {0, 0, 0, 0};
     // small host arrays that accompany MDB_MEM_DEVICE calls (per-query user slots): those calls return without a sync, so
@@ -153,7 +152,9 @@ struct mdb_ctx {
     // context is destroyed with the last handle (so free order does not matter to the caller)
     std::atomic<int> refs{1};
 };
-mdb_status mdb_pinned(mdb_ctx* ctx, int slot, size_t bytes, void** out);  // grow-only pinned host buffer
+// roles of mdb_ctx::pinned: inputs, outputs, per-call filter bitmaps, small auxiliary inputs (per-query user indices, probe lists)
+enum mdb_pin { MDB_PIN_IN = 0, MDB_PIN_OUT = 1, MDB_PIN_FILTER = 2, MDB_PIN_AUX = 3 };
+mdb_status mdb_pinned(mdb_ctx* ctx, mdb_pin role, size_t bytes, void** out);  // grow-only pinned host buffer
 // host -> device copy of a small array, enqueued on the stream; `src` may be reused at once, and so may the call
 mdb_status mdb_stage_small(mdb_ctx* ctx, const void* src, size_t bytes, void* d_dst);
 struct HostCopy { void* dst; const void* src; size_t bytes; };
@@ -209,8 +210,22 @@ static inline mdb_status mdb_require_idle(mdb_ctx* ctx, mdb_mem mem) {
         return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "a submitted call is pending on this context: call mdb_wait first");
     return MDB_OK;
 }
-// grow-only scratch slot
-mdb_status mdb_scratch(mdb_ctx* ctx, int slot, size_t bytes, void** out);
+// a device buffer of the API call in progress, from the context's arena: 256-byte aligned, valid until the next call begins
+mdb_status mdb_scratch(mdb_ctx* ctx, size_t bytes, void** out);
+mdb_status mdb_begin_call(mdb_ctx* ctx);
+// opens an API call — an extern "C" entry, or the one body its variants share; never a function that runs inside a call: takes the
+// context's lock, selects its device, begins the call's scratch (everything mdb_scratch handed out before is dead)
+#define MDB_ENTER(ctx)                                   \
+    std::lock_guard<std::mutex> _mdb_lock((ctx)->mu);    \
+    MDB_HIP((ctx), hipSetDevice((ctx)->device));         \
+    MDB_TRY(mdb_begin_call(ctx))
+// mdb_*_search_submit: mdb_return_to_host enqueues instead of synchronising
+struct SubmitScope {
+    mdb_ctx* c;
+    bool on;
+    SubmitScope(mdb_ctx* c_, bool on_) : c(c_), on(on_) { if (on) c->submit_mode = true; }
+    ~SubmitScope() { if (on) c->submit_mode = false; }
+};
 // check the device flag word after a synchronising call
 mdb_status mdb_check_flags(mdb_ctx* ctx);
 

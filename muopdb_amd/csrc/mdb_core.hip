@@ -1,4 +1,4 @@
-// mdb_core.hip — context, scratch, error plumbing and the unit-test seams of the C ABI
+// mdb_core.hip — context, scratch arena, error plumbing and the unit-test seams of the C ABI
 // (distance pairs, PQ quantize / distance, Elias-Fano decode).
 #include <cstdarg>
 
@@ -16,21 +16,21 @@ mdb_status mdb_fail(mdb_ctx* ctx, mdb_status st, const char* fmt, ...) {
     return st;
 }
 
-mdb_status mdb_scratch(mdb_ctx* ctx, int slot, size_t bytes, void** out) {
-    if (bytes == 0) bytes = 16;
-    if (ctx->scratch_cap[slot] < bytes) {
-        if (ctx->scratch[slot]) {
-            MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            MDB_HIP(ctx, hipFree(ctx->scratch[slot]));
-            ctx->scratch[slot] = nullptr;
-            ctx->scratch_cap[slot] = 0;
-        }
-        size_t cap = bytes + bytes / 4;
-        hipError_t e = hipMalloc(&ctx->scratch[slot], cap);
-        if (e != hipSuccess) return mdb_fail(ctx, MDB_ERR_OOM, "hipMalloc(%zu) failed: %s", cap, hipGetErrorString(e));
-        ctx->scratch_cap[slot] = cap;
-    }
-    *out = ctx->scratch[slot];
+static mdb_status arena_oom(mdb_ctx* ctx) {
+    return mdb_fail(ctx, MDB_ERR_OOM, "hipMalloc(%zu) failed: %s", ctx->arena.fail_bytes, hipGetErrorString((hipError_t)ctx->arena.fail_code));
+}
+
+mdb_status mdb_begin_call(mdb_ctx* ctx) { return ctx->arena.begin() ? MDB_OK : arena_oom(ctx); }
+
+mdb_status mdb_scratch(mdb_ctx* ctx, size_t bytes, void** out) {
+    *out = ctx->arena.alloc(bytes);
+    return *out ? MDB_OK : arena_oom(ctx);
+}
+
+static mdb_status flags_to_status(mdb_ctx* ctx, uint32_t f) {
+    if (f & MDB_FLAG_NAN) return mdb_fail(ctx, MDB_ERR_NAN, "a distance evaluated to NaN (reference: NotNan::new(..).unwrap() panics)");
+    if (f & MDB_FLAG_OVERFLOW) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "traversal state exceeded the on-chip capacity");
+    if (f & MDB_FLAG_RANGE) return mdb_fail(ctx, MDB_ERR_FORMAT, "index refers to a point id outside the vector storage");
     return MDB_OK;
 }
 
@@ -38,14 +38,10 @@ mdb_status mdb_check_flags(mdb_ctx* ctx) {
     MDB_HIP(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
     MDB_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, 4, ctx->stream));
     MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t f = *ctx->h_flags;
-    if (f & MDB_FLAG_NAN) return mdb_fail(ctx, MDB_ERR_NAN, "a distance evaluated to NaN (reference: NotNan::new(..).unwrap() panics)");
-    if (f & MDB_FLAG_OVERFLOW) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "traversal state exceeded the on-chip capacity");
-    if (f & MDB_FLAG_RANGE) return mdb_fail(ctx, MDB_ERR_FORMAT, "index refers to a point id outside the vector storage");
-    return MDB_OK;
+    return flags_to_status(ctx, *ctx->h_flags);
 }
 
-mdb_status mdb_pinned(mdb_ctx* ctx, int slot, size_t bytes, void** out) {
+mdb_status mdb_pinned(mdb_ctx* ctx, mdb_pin slot, size_t bytes, void** out) {
     if (bytes > ctx->pinned_cap[slot]) {
         MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->pinned[slot]) (void)hipHostFree(ctx->pinned[slot]);
@@ -83,7 +79,7 @@ mdb_status mdb_return_to_host(mdb_ctx* ctx, const HostCopy* items, int n) {
     size_t total = 0;
     for (int i = 0; i < n; ++i) total += align_up(items[i].dst && items[i].bytes ? items[i].bytes : 0, 64);
     char* stage = nullptr;
-    if (total) MDB_TRY(mdb_pinned(ctx, 1, total, (void**)&stage));
+    if (total) MDB_TRY(mdb_pinned(ctx, MDB_PIN_OUT, total, (void**)&stage));
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         if (!items[i].dst || !items[i].bytes) continue;
@@ -113,13 +109,6 @@ mdb_status mdb_return_to_host(mdb_ctx* ctx, const HostCopy* items, int n) {
     return st;
 }
 
-static mdb_status flags_to_status(mdb_ctx* ctx, uint32_t f) {
-    if (f & MDB_FLAG_NAN) return mdb_fail(ctx, MDB_ERR_NAN, "a distance evaluated to NaN (reference: NotNan::new(..).unwrap() panics)");
-    if (f & MDB_FLAG_OVERFLOW) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "traversal state exceeded the on-chip capacity");
-    if (f & MDB_FLAG_RANGE) return mdb_fail(ctx, MDB_ERR_FORMAT, "index refers to a point id outside the vector storage");
-    return MDB_OK;
-}
-
 extern "C" mdb_status mdb_wait(mdb_ctx* ctx) {
     if (!ctx) return MDB_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->mu);
@@ -127,7 +116,7 @@ extern "C" mdb_status mdb_wait(mdb_ctx* ctx) {
     MDB_HIP(ctx, hipSetDevice(ctx->device));
     MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_pending = false;
-    const char* stage = (const char*)ctx->pinned[1];
+    const char* stage = (const char*)ctx->pinned[MDB_PIN_OUT];
     for (auto& c : ctx->pending) memcpy(c.dst, stage + c.off, c.bytes);
     ctx->pending.clear();
     return flags_to_status(ctx, *ctx->h_flags);
@@ -149,8 +138,7 @@ void mdb_ctx_release(mdb_ctx* ctx) {
     if (ctx->refs.fetch_sub(1) != 1) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (size_t i = 0; i < sizeof(ctx->scratch) / sizeof(ctx->scratch[0]); ++i)
-        if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
+    ctx->arena.release_all();
     if (ctx->d_flags) (void)hipFree(ctx->d_flags);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
@@ -176,6 +164,12 @@ mdb_status mdb_device_open(int gpu, mdb_ctx** out) {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || gpu < 0 || gpu >= count) return MDB_ERR_HIP;
     mdb_ctx* ctx = new mdb_ctx();
     ctx->device = gpu;
+    ctx->arena.user = ctx;
+    ctx->arena.alloc_cb = [](void*, size_t bytes, void** out) { return (int)hipMalloc(out, bytes); };
+    ctx->arena.release_cb = [](void* c, void* p) {   // an earlier call's kernels may still use the chunk
+        (void)hipStreamSynchronize(((mdb_ctx*)c)->stream);
+        (void)hipFree(p);
+    };
     if (hipSetDevice(gpu) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void**)&ctx->d_flags, 4) != hipSuccess || hipHostMalloc((void**)&ctx->h_flags, 4) != hipSuccess ||
         hipMemset(ctx->d_flags, 0, 4) != hipSuccess || hipMalloc((void**)&ctx->d_counters, 256) != hipSuccess ||
@@ -285,8 +279,7 @@ const char* mdb_last_error(mdb_ctx* ctx) { return ctx ? ctx->last_error.c_str() 
 
 mdb_status mdb_device_mem_info(mdb_ctx* ctx, size_t* free_bytes, size_t* total_bytes) {
     if (!ctx || !free_bytes || !total_bytes) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     MDB_HIP(ctx, hipMemGetInfo(free_bytes, total_bytes));
     return MDB_OK;
@@ -336,16 +329,14 @@ __global__ __launch_bounds__(256) void pair_distance_kernel(const float* __restr
 
 static mdb_status pair_distance(mdb_ctx* ctx, int metric, const float* a, const float* b, size_t n, size_t d, int squared,
                                 float* out) {
-    if (!ctx || !a || !b || !out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    if (!a || !b || !out) return MDB_ERR_INVALID_ARG;
     if (n == 0) return MDB_OK;
     // q pointer reads up to 4 floats past a row's tail chunk only when ntail>0 and j<ntail is false -> never
     // dereferenced beyond d; b uses the bounds-checked RowLoader.  Pad `a` by 4 floats to be safe.
     void *da, *db, *dout;
-    MDB_TRY(mdb_scratch(ctx, 0, (n * d + 4) * 4, &da));
-    MDB_TRY(mdb_scratch(ctx, 1, (n * d + 4) * 4, &db));
-    MDB_TRY(mdb_scratch(ctx, 2, n * 4, &dout));
+    MDB_TRY(mdb_scratch(ctx, (n * d + 4) * 4, &da));
+    MDB_TRY(mdb_scratch(ctx, (n * d + 4) * 4, &db));
+    MDB_TRY(mdb_scratch(ctx, n * 4, &dout));
     MDB_HIP(ctx, hipMemcpyAsync(da, a, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
     MDB_HIP(ctx, hipMemcpyAsync(db, b, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
     DistPlan p = make_plan((int)d, metric);
@@ -362,9 +353,13 @@ static mdb_status pair_distance(mdb_ctx* ctx, int metric, const float* a, const 
 
 extern "C" mdb_status mdb_l2_distance(mdb_ctx* ctx, const float* a, const float* b, size_t n, size_t d, int squared,
                                       float* out) {
+    if (!ctx) return MDB_ERR_INVALID_ARG;
+    MDB_ENTER(ctx);
     return pair_distance(ctx, MDB_METRIC_L2, a, b, n, d, squared, out);
 }
 extern "C" mdb_status mdb_dot_distance(mdb_ctx* ctx, const float* a, const float* b, size_t n, size_t d, float* out) {
+    if (!ctx) return MDB_ERR_INVALID_ARG;
+    MDB_ENTER(ctx);
     return pair_distance(ctx, MDB_METRIC_DOT, a, b, n, d, 0, out);
 }
 
@@ -390,14 +385,13 @@ __global__ __launch_bounds__(256) void lane_conforming_kernel(const float* __res
 extern "C" mdb_status mdb_lane_conforming_distance(mdb_ctx* ctx, const float* a, const float* b, size_t n, size_t d, int lanes,
                                                    mdb_metric metric, float* out) {
     if (!ctx || !a || !b || !out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
+    MDB_ENTER(ctx);
     if (lanes != 4 && lanes != 8 && lanes != 16) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "lanes must be 4, 8 or 16");
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return MDB_OK;
     void *da, *db, *dout;
-    MDB_TRY(mdb_scratch(ctx, 0, (n * d + 4) * 4, &da));
-    MDB_TRY(mdb_scratch(ctx, 1, (n * d + 4) * 4, &db));
-    MDB_TRY(mdb_scratch(ctx, 2, n * 4, &dout));
+    MDB_TRY(mdb_scratch(ctx, (n * d + 4) * 4, &da));
+    MDB_TRY(mdb_scratch(ctx, (n * d + 4) * 4, &db));
+    MDB_TRY(mdb_scratch(ctx, n * 4, &dout));
     MDB_HIP(ctx, hipMemcpyAsync(da, a, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
     MDB_HIP(ctx, hipMemcpyAsync(db, b, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
     dim3 grid((unsigned)((n + 255) / 256));
@@ -521,14 +515,13 @@ __global__ __launch_bounds__(256) void pq_pair_distance_kernel(const uint8_t* __
 extern "C" mdb_status mdb_pq_quantize(mdb_ctx* ctx, const mdb_quant_desc* q, const float* vectors, size_t n,
                                       uint8_t* codes_out) {
     if (!ctx || !q || !vectors || !codes_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     PqDev pq;
     MDB_TRY(pq_upload(ctx, q, pq));
     if (n == 0) return MDB_OK;
     void *dv, *dc;
-    MDB_TRY(mdb_scratch(ctx, 0, (n * pq.dimension + 4) * 4, &dv));
-    MDB_TRY(mdb_scratch(ctx, 1, n * pq.m, &dc));
+    MDB_TRY(mdb_scratch(ctx, (n * pq.dimension + 4) * 4, &dv));
+    MDB_TRY(mdb_scratch(ctx, n * pq.m, &dc));
     MDB_HIP(ctx, hipMemcpyAsync(dv, vectors, n * pq.dimension * 4, hipMemcpyHostToDevice, ctx->stream));
     MDB_TRY(pq_quantize_device(ctx, pq, (float*)dv, n, (uint8_t*)dc));
     MDB_HIP(ctx, hipMemcpyAsync(codes_out, dc, n * pq.m, hipMemcpyDeviceToHost, ctx->stream));
@@ -540,8 +533,7 @@ extern "C" mdb_status mdb_pq_quantize_mem(mdb_ctx* ctx, const mdb_quant_desc* q,
                                           uint8_t* codes_out) {
     if (mem != MDB_MEM_DEVICE) return mdb_pq_quantize(ctx, q, vectors, n, codes_out);
     if (!ctx || !q || !vectors || !codes_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     PqDev pq;
     MDB_TRY(pq_upload(ctx, q, pq));
     if (n == 0) return MDB_OK;
@@ -563,15 +555,14 @@ __global__ void pq_original_vector_kernel(const uint8_t* __restrict__ codes, int
 
 extern "C" mdb_status mdb_pq_original_vector(mdb_ctx* ctx, const mdb_quant_desc* q, const uint8_t* codes, size_t n, float* vectors_out) {
     if (!ctx || !q || !codes || !vectors_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     PqDev pq;
     MDB_TRY(pq_upload(ctx, q, pq));
     if (n == 0) return MDB_OK;
     const size_t total = n * (size_t)pq.m * pq.subdim;
     void *dc, *dv;
-    MDB_TRY(mdb_scratch(ctx, 1, n * pq.m, &dc));
-    MDB_TRY(mdb_scratch(ctx, 0, total * 4, &dv));
+    MDB_TRY(mdb_scratch(ctx, n * pq.m, &dc));
+    MDB_TRY(mdb_scratch(ctx, total * 4, &dv));
     MDB_HIP(ctx, hipMemcpyAsync(dc, codes, n * pq.m, hipMemcpyHostToDevice, ctx->stream));
     pq_original_vector_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, ctx->stream>>>((const uint8_t*)dc, pq.m, pq.subdim, pq.K,
                                                                                             pq.codebook.p, (float*)dv, total);
@@ -584,15 +575,14 @@ extern "C" mdb_status mdb_pq_original_vector(mdb_ctx* ctx, const mdb_quant_desc*
 extern "C" mdb_status mdb_pq_distance(mdb_ctx* ctx, const mdb_quant_desc* q, const uint8_t* a, const uint8_t* b, size_t n,
                                       mdb_distance_impl impl, float* out) {
     if (!ctx || !q || !a || !b || !out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     PqDev pq;
     MDB_TRY(pq_upload(ctx, q, pq));
     if (n == 0) return MDB_OK;
     void *da, *db, *dout;
-    MDB_TRY(mdb_scratch(ctx, 0, n * pq.m, &da));
-    MDB_TRY(mdb_scratch(ctx, 1, n * pq.m, &db));
-    MDB_TRY(mdb_scratch(ctx, 2, n * 4, &dout));
+    MDB_TRY(mdb_scratch(ctx, n * pq.m, &da));
+    MDB_TRY(mdb_scratch(ctx, n * pq.m, &db));
+    MDB_TRY(mdb_scratch(ctx, n * 4, &dout));
     MDB_HIP(ctx, hipMemcpyAsync(da, a, n * pq.m, hipMemcpyHostToDevice, ctx->stream));
     MDB_HIP(ctx, hipMemcpyAsync(db, b, n * pq.m, hipMemcpyHostToDevice, ctx->stream));
     DistPlan sp = make_plan(pq.subdim, pq.metric), spl2 = make_plan(pq.subdim, MDB_METRIC_L2);

@@ -77,16 +77,15 @@ mdb_status ef_decode_lists(mdb_ctx* ctx, const uint8_t* d_bytes, const uint64_t*
 extern "C" mdb_status mdb_ef_decode(mdb_ctx* ctx, const uint8_t* blob, size_t blob_len, uint64_t* out, size_t cap,
                                     size_t* n_out) {
     if (!ctx || !blob || !n_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (const char* why = ef_header_error(blob, blob_len, (blob_len / 8) * 64)) return mdb_fail(ctx, MDB_ERR_FORMAT, "%s", why);
     uint64_t n = rd_u64(blob);
     *n_out = n;
     if (n == 0) return MDB_OK;
     void *db, *dmeta, *dout;
-    MDB_TRY(mdb_scratch(ctx, 0, blob_len + 16, &db));
-    MDB_TRY(mdb_scratch(ctx, 1, 16, &dmeta));
-    MDB_TRY(mdb_scratch(ctx, 2, n * 8, &dout));
+    MDB_TRY(mdb_scratch(ctx, blob_len + 16, &db));
+    MDB_TRY(mdb_scratch(ctx, 16, &dmeta));
+    MDB_TRY(mdb_scratch(ctx, n * 8, &dout));
     uint64_t meta[2] = {0, 0};
     MDB_HIP(ctx, hipMemcpyAsync(db, blob, blob_len, hipMemcpyHostToDevice, ctx->stream));
     MDB_HIP(ctx, hipMemcpyAsync(dmeta, meta, 16, hipMemcpyHostToDevice, ctx->stream));

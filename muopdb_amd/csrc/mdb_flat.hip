@@ -57,7 +57,7 @@ __global__ void pad_queries_kernel(const float* __restrict__ q, size_t b, int d,
     out[t] = (row < b && e < d) ? q[row * d + e] : 0.0f;
 }
 
-mdb_status stage_queries(mdb_ctx* ctx, int slot, const float* queries, size_t b, int d, mdb_mem mem, size_t bpad,
+mdb_status stage_queries(mdb_ctx* ctx, const float* queries, size_t b, int d, mdb_mem mem, size_t bpad,
                          float** d_out, int* qstride) {
     if (mem == MDB_MEM_DEVICE && (b == bpad || b % 4 == 0) && d % 16 == 0 && ((uintptr_t)queries & 15) == 0 && !ctx->opt.no_inplace) {
         // device-resident f32 rows that are whole 16-float chunks, in a batch of whole query groups: every kernel reads the
@@ -71,16 +71,16 @@ mdb_status stage_queries(mdb_ctx* ctx, int slot, const float* queries, size_t b,
     }
     int qs = ((d + 3) / 4) * 4 + 16;  // +16: exact_sums may form (never dereference) pointers past the row
     void* dq;
-    MDB_TRY(mdb_scratch(ctx, slot, bpad * (size_t)qs * 4 + 64, &dq));
+    MDB_TRY(mdb_scratch(ctx, bpad * (size_t)qs * 4 + 64, &dq));
     const float* src = queries;
     if (mem == MDB_MEM_HOST) {
-        if (ctx->has_pending) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "a submitted call is pending on this context: call mdb_wait first");
+        MDB_TRY(mdb_require_idle(ctx, mem));
         void* raw;
-        MDB_TRY(mdb_scratch(ctx, slot + 1, b * (size_t)d * 4 + 16, &raw));
+        MDB_TRY(mdb_scratch(ctx, b * (size_t)d * 4 + 16, &raw));
         // caller's (pageable) rows -> pinned staging on the CPU, then a true async copy; every MDB_MEM_HOST call ends with a
         // stream sync, so the staging block is free again when the next call starts
         void* pin;
-        MDB_TRY(mdb_pinned(ctx, 0, b * (size_t)d * 4, &pin));
+        MDB_TRY(mdb_pinned(ctx, MDB_PIN_IN, b * (size_t)d * 4, &pin));
         memcpy(pin, queries, b * (size_t)d * 4);
         MDB_HIP(ctx, hipMemcpyAsync(raw, pin, b * (size_t)d * 4, hipMemcpyHostToDevice, ctx->stream));
         src = (const float*)raw;
@@ -712,7 +712,7 @@ mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const fl
     if (b <= 4 && k >= 1 && k <= 64 && ts.ntiles >= 1 && ts.ntiles <= 1024 && p.n16 >= 1 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 &&
         !gate && ctx->opt.flat_no_small != 1) {
         void* partial;
-        MDB_TRY(mdb_scratch(ctx, 4, (size_t)ts.ntiles * b * MDB_TILE * 8, &partial));
+        MDB_TRY(mdb_scratch(ctx, (size_t)ts.ntiles * b * MDB_TILE * 8, &partial));
         const bool sorted = ctx->opt.flat_no_small != 2;   // 2: the waves store their keys unordered, the merge bounds 1024 thread groups (measured slower)
         // MDB_FLAT_NO_SMALL=4: ONE launch (flat_small_block_kernel: a ticket per BLOCK of 16 tiles; k <= 16, at most 64 blocks).  Measured on C1:
         // 13.5 us against 5.1 + 6.0 for the two launches, with ten tickets — the hand-over is three dependent trips to the memory side
@@ -764,7 +764,7 @@ mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const fl
     // keep the partial buffer bounded (<= 256 MiB)
     while (nblk > 32 && (size_t)nblk * bpad * std::max<size_t>(k, 1) * 8 > (256u << 20)) nblk /= 2;
     void* partial;
-    MDB_TRY(mdb_scratch(ctx, 4, (size_t)nblk * bpad * std::max<size_t>(k, 1) * 8, &partial));
+    MDB_TRY(mdb_scratch(ctx, (size_t)nblk * bpad * std::max<size_t>(k, 1) * 8, &partial));
     bool saved = ctx->prof_on;
     ctx->prof_on = saved && profile;
     {
@@ -798,8 +798,7 @@ mdb_status mdb_flat_create(mdb_ctx* ctx, const float* base, size_t n, size_t d, 
                            mdb_flat** out) {
     if (!ctx || !out || (!base && n) || d == 0) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     mdb_flat* f = new mdb_flat;
     f->ctx = ctx;
     f->metric = (int)metric;
@@ -837,8 +836,7 @@ mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_
                            float* dist_out, uint32_t* counts_out) {
     if (!flat || (!queries && b) || !ids_out || !dist_out) return MDB_ERR_INVALID_ARG;
     mdb_ctx* ctx = flat->ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (b == 0) return MDB_OK;
     if (k > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
     float* dq;
@@ -846,11 +844,11 @@ mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_
     const bool batched = flat_mfma_applicable(ctx, view_of(flat->ts), flat->aux, b, k);
     // whole query groups of the matrix-core filter (up to 8 x 32 rows) / of the exact scan (flat_choose_qt: one query is its own group)
     const size_t bpad = batched ? (b + 255) / 256 * 256 : (b == 1 ? 1 : (b + 3) / 4 * 4);
-    MDB_TRY(stage_queries(ctx, 0, queries, b, flat->ts.d, mem, bpad, &dq, &qstride));
+    MDB_TRY(stage_queries(ctx, queries, b, flat->ts.d, mem, bpad, &dq, &qstride));
     void *keys, *cnts;
     bool fused = false;
-    MDB_TRY(mdb_scratch(ctx, 5, b * std::max<size_t>(k, 1) * 8, &keys));
-    MDB_TRY(mdb_scratch(ctx, 6, b * 4, &cnts));
+    MDB_TRY(mdb_scratch(ctx, b * std::max<size_t>(k, 1) * 8, &keys));
+    MDB_TRY(mdb_scratch(ctx, b * 4, &cnts));
     if (batched) {
         // device outputs: the last merge kernel of the batched path writes the caller's rows itself
         UnpackOut up{ids_out, dist_out, counts_out};
@@ -880,8 +878,8 @@ mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_
         return MDB_OK;
     }
     void *dids, *ddist;
-    MDB_TRY(mdb_scratch(ctx, 2, total * 4, &dids));
-    MDB_TRY(mdb_scratch(ctx, 3, total * 4, &ddist));
+    MDB_TRY(mdb_scratch(ctx, total * 4, &dids));
+    MDB_TRY(mdb_scratch(ctx, total * 4, &ddist));
     if (total) unpack_keys_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, ctx->stream>>>((uint64_t*)keys, total, (uint32_t*)dids, (float*)ddist);
     MDB_HIP(ctx, hipGetLastError());
     const HostCopy back[3] = {{ids_out, dids, total * 4}, {dist_out, ddist, total * 4}, {counts_out, cnts, b * 4}};
@@ -923,8 +921,7 @@ mdb_status mdb_ivf_assign(mdb_ctx* ctx, const float* centroids, size_t num_centr
                           size_t max_clusters_per_vector, float distance_threshold, mdb_mem mem, uint32_t* centroid_ids_out,
                           uint32_t* counts_out) {
     if (!ctx || (!centroids && num_centroids) || (!vectors && n) || !centroid_ids_out || !counts_out || d == 0) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     const size_t mc = max_clusters_per_vector;
     if (mc == 0 || mc > num_centroids)
         return mdb_fail(ctx, MDB_ERR_OUT_OF_RANGE, "max_clusters_per_vector=%zu out of range (num_centroids=%zu): the reference panics in select_nth_unstable_by", mc, num_centroids);
@@ -945,15 +942,16 @@ mdb_status mdb_ivf_assign(mdb_ctx* ctx, const float* centroids, size_t num_centr
     }
     const size_t CH = 1 << 16;  // vectors per pass
     void *keys, *cnts, *dids, *dcn;
-    MDB_TRY(mdb_scratch(ctx, 5, CH * mc * 8, &keys));
-    MDB_TRY(mdb_scratch(ctx, 6, CH * 4, &cnts));
-    MDB_TRY(mdb_scratch(ctx, 2, CH * mc * 4, &dids));
-    MDB_TRY(mdb_scratch(ctx, 3, CH * 4, &dcn));
+    MDB_TRY(mdb_scratch(ctx, CH * mc * 8, &keys));
+    MDB_TRY(mdb_scratch(ctx, CH * 4, &cnts));
+    MDB_TRY(mdb_scratch(ctx, CH * mc * 4, &dids));
+    MDB_TRY(mdb_scratch(ctx, CH * 4, &dcn));
     for (size_t s0 = 0; s0 < n; s0 += CH) {
         const size_t b = std::min(CH, n - s0);
+        const mdb_arena::Mark pass = ctx->arena.mark();   // the pass's staging and partial lists: given back at its end
         float* dq;
         int qstride;
-        MDB_TRY(stage_queries(ctx, 0, vectors + s0 * d, b, (int)d, mem, (b + 3) / 4 * 4, &dq, &qstride));
+        MDB_TRY(stage_queries(ctx, vectors + s0 * d, b, (int)d, mem, (b + 3) / 4 * 4, &dq, &qstride));
         // L2DistanceCalculator::calculate_squared (:276) — no sqrt
         MDB_TRY(flat_topk_keys(ctx, view_of(cs), MDB_METRIC_L2SQ, dq, qstride, b, mc, (uint64_t*)keys, (uint32_t*)cnts, false));
         uint32_t* oi = mem == MDB_MEM_DEVICE ? centroid_ids_out + s0 * mc : (uint32_t*)dids;
@@ -966,6 +964,7 @@ mdb_status mdb_ivf_assign(mdb_ctx* ctx, const float* centroids, size_t num_centr
             MDB_HIP(ctx, hipMemcpyAsync(counts_out + s0, dcn, b * 4, hipMemcpyDeviceToHost, ctx->stream));
             MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
+        ctx->arena.rewind(pass);
     }
     return mdb_check_flags(ctx);
 }

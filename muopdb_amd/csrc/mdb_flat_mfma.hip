@@ -1438,7 +1438,7 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
     char* ax;
     size_t off_sc = align_up(b * k * 8, 16), off_cr = off_sc + align_up(b * 4, 16), off_qn = off_cr + align_up(bpadq * 4, 256),
            off_np = off_qn + align_up(bpadq * 4, 256), off_ov = off_np + bpadq * (size_t)QCNT_STRIDE * 4, off_qc = off_ov + 256;
-    MDB_TRY(mdb_scratch(ctx, 8, off_qc + bpadq * (size_t)qstride * 4, (void**)&ax));
+    MDB_TRY(mdb_scratch(ctx, off_qc + bpadq * (size_t)qstride * 4, (void**)&ax));
     uint64_t* skeys = (uint64_t*)ax;
     uint32_t* scounts = (uint32_t*)(ax + off_sc);
     float* crow = (float*)(ax + off_cr);
@@ -1450,7 +1450,7 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
     uint32_t qcap = MF_CAP;
     while (qcap > 512 && bpadq * (size_t)qcap * 4 > ((size_t)1 << 30)) qcap /= 2;
     uint32_t* qids;
-    MDB_TRY(mdb_scratch(ctx, 9, bpadq * (size_t)qcap * 4, (void**)&qids));
+    MDB_TRY(mdb_scratch(ctx, bpadq * (size_t)qcap * 4, (void**)&qids));
     // A. bound of the k-th distance from the sample: its exact top-k (f32 route), or the k-th smallest of matrix-core upper
     //    bounds (bf16 route: no exact pass over the sample at all — the U matrix must fit 1 GiB, else the exact sample scan)
     const bool x1 = use_bf16 && (ctx->opt.bf_x1 >= 2 || (ctx->opt.bf_x1 == 1 && metric == MDB_METRIC_L2) || !aux.blo.p);   // one bf16 product per pair (below); always when the store holds no lo halves
@@ -1466,7 +1466,7 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
     const size_t ns = xbound ? (size_t)gridxb.x * 32 : aux.sample.n;
     const bool smp_bf16 = use_bf16 && aux.sample_stride && k <= SB_SUB / 4 && b * ns * 4 <= ((size_t)1 << 30) && !ctx->opt.bf_exact_sample;
     float* umat = nullptr;
-    if (smp_bf16) MDB_TRY(mdb_scratch(ctx, 12, b * ns * 4, (void**)&umat));
+    if (smp_bf16) MDB_TRY(mdb_scratch(ctx, b * ns * 4, (void**)&umat));
     else MDB_TRY(flat_topk_keys(ctx, view_of(aux.sample), metric, dq, qstride, b, k, skeys, scounts, false));
     // large batches over a store with a row-major copy (a coarse quantizer) are refined one block per query, and the filter hands
     // its products over with the candidates (flat_refine_group_kernel)
@@ -1476,7 +1476,7 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
     const bool by_groups = aux.rows.p && b >= (size_t)std::max<long long>(0, ctx->opt.refine_group_min_b) && k <= 256 && !ctx->opt.refine_no_groups &&
                            (size_t)(RG_CAP + RG_SURV) * 8 + k * 8 + 260 * 4 + (size_t)RG_CAP * 4 + (size_t)ts.d4 * 16 <= 48 * 1024;
     float* qapx = nullptr;
-    if (by_groups && smp_bf16 && !ctx->opt.refine_no_second_bound) MDB_TRY(mdb_scratch(ctx, 10, bpadq * (size_t)qcap * 4, (void**)&qapx));
+    if (by_groups && smp_bf16 && !ctx->opt.refine_no_second_bound) MDB_TRY(mdb_scratch(ctx, bpadq * (size_t)qcap * 4, (void**)&qapx));
     // error budget of the filter, eps = 2^-24, all norms of the centred operands:
     //   centring (eps per component)            : |a' - ||q-x||^2| <= 4 eps (qn + xn)
     //   reference association vs real arithmetic: s_ref >= s* (1 - (d+2) eps)  -> 2(d+3) eps (qn + xn)
@@ -1618,7 +1618,7 @@ mdb_status flat_topk_keys_mfma(mdb_ctx* ctx, const TileView& ts, FlatAux& aux, i
     // 256-thread slices: fewer, larger ones measured 2.5x slower (a block's rounds are latency bound); one-wave slices: 4 beat 8 and 16
     // (C5 coarse: refine 157 / 167 / 175 us, merge 23 / 34 / 38 us)
     const unsigned rs = rs_env ? rs_env : (wave_slices ? 4 : MF_RS);
-    MDB_TRY(mdb_scratch(ctx, 10, b * (size_t)rs * std::max<size_t>(k, 1) * 8, (void**)&rpart));
+    MDB_TRY(mdb_scratch(ctx, b * (size_t)rs * std::max<size_t>(k, 1) * 8, (void**)&rpart));
     const bool rows = aux.rows.p != nullptr;
     const float4* rsrc = rows ? (const float4*)aux.rows.p : (const float4*)ts.data;
     MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {

@@ -1746,8 +1746,8 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
     if (kind == MDB_QUANT_PQ) {
         // the query is quantized like a stored point (index.rs:168) and written out as its codebook rows
         void *qcodes, *qrows;
-        MDB_TRY(mdb_scratch(ctx, 7, b * (size_t)pq.m + 16, &qcodes));
-        MDB_TRY(mdb_scratch(ctx, 2, b * (size_t)qstride * 4 + 16, &qrows));
+        MDB_TRY(mdb_scratch(ctx, b * (size_t)pq.m + 16, &qcodes));
+        MDB_TRY(mdb_scratch(ctx, b * (size_t)qstride * 4 + 16, &qrows));
         MDB_TRY(pq_quantize_device(ctx, pq, d_q, b, (uint8_t*)qcodes, qstride));
         size_t tq = b * (size_t)qstride;
         pq_rows_kernel<<<dim3((unsigned)((tq + 255) / 256)), 256, 0, ctx->stream>>>((const uint8_t*)qcodes, nullptr, (size_t)pq.m, pq.m,
@@ -1774,7 +1774,7 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
     a.vis_words = words;
     if (!vis_lds) {
         void* vg;
-        MDB_TRY(mdb_scratch(ctx, 4, b * words * 4, &vg));
+        MDB_TRY(mdb_scratch(ctx, b * words * 4, &vg));
         MDB_HIP(ctx, hipMemsetAsync(vg, 0, b * words * 4, ctx->stream));
         a.vis_global = (uint32_t*)vg;
     }
@@ -1837,10 +1837,10 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
     if (table) {
         const uint32_t words = (upper.nu / 32 + 4) & ~3u;   // a multiple of 4: hnsw_upper_kernel puts the table row's LDS copy (16-byte stores) behind the bitmap
         void *tab, *st;
-        MDB_TRY(mdb_scratch(ctx, 8, (size_t)b * nu_pad * 4 + 64, &tab));
-        MDB_TRY(mdb_scratch(ctx, 9, (size_t)b * (words + 6) * 4 + 64, &st));
+        MDB_TRY(mdb_scratch(ctx, (size_t)b * nu_pad * 4 + 64, &tab));
+        MDB_TRY(mdb_scratch(ctx, (size_t)b * (words + 6) * 4 + 64, &st));
         void* st2;
-        MDB_TRY(mdb_scratch(ctx, 10, ((size_t)b * (words + 8) + 64) * 4, &st2));
+        MDB_TRY(mdb_scratch(ctx, ((size_t)b * (words + 8) + 64) * 4, &st2));
         HnswUpperOut uo;
         uo.ep = (uint32_t*)st;
         uo.ovf = uo.ep + b;
@@ -1917,8 +1917,7 @@ mdb_status mdb_hnsw_load(mdb_ctx* ctx, const void* index_bytes, size_t index_len
                          mdb_hnsw** out) {
     if (!ctx || !index_bytes || !vectors_bytes || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if ((size_t)index_offset + 9 > index_len) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW index: header out of bounds");
     uint32_t dim = quant && quant->dimension ? quant->dimension : rd_u32((const uint8_t*)index_bytes + index_offset + 1);
     mdb_hnsw* h = new mdb_hnsw();
@@ -1971,14 +1970,9 @@ static mdb_status hnsw_ann_search_impl(mdb_hnsw* h, const float* queries, size_t
     if (!h || (!queries && b) || !doc_ids_out || !scores_out) return MDB_ERR_INVALID_ARG;
     HnswSet& s = h->set;
     mdb_ctx* ctx = s.ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (b == 0) return MDB_OK;
-    struct SubmitScope {  // mdb_hnsw_ann_search_submit: mdb_return_to_host enqueues instead of synchronising
-        mdb_ctx* c; bool on;
-        SubmitScope(mdb_ctx* c_, bool on_) : c(c_), on(on_) { if (on) c->submit_mode = true; }
-        ~SubmitScope() { if (on) c->submit_mode = false; }
-    } submit_scope(ctx, submit && mem == MDB_MEM_HOST);
+    SubmitScope submit_scope(ctx, submit && mem == MDB_MEM_HOST);
     if (k > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
     float* dq;
     int qstride;
@@ -1987,11 +1981,11 @@ static mdb_status hnsw_ann_search_impl(mdb_hnsw* h, const float* queries, size_t
         dq = const_cast<float*>(queries);
         qstride = (int)s.dimension;
     } else {
-        MDB_TRY(stage_queries(ctx, 0, queries, b, (int)s.dimension, mem, b, &dq, &qstride));
+        MDB_TRY(stage_queries(ctx, queries, b, (int)s.dimension, mem, b, &dq, &qstride));
     }
     void *keys, *cnts;
-    MDB_TRY(mdb_scratch(ctx, 3, b * std::max<size_t>(k, 1) * 8, &keys));
-    MDB_TRY(mdb_scratch(ctx, 6, b * 4 + 16, &cnts));
+    MDB_TRY(mdb_scratch(ctx, b * std::max<size_t>(k, 1) * 8, &keys));
+    MDB_TRY(mdb_scratch(ctx, b * 4 + 16, &cnts));
     ctx->dev_counters = true;
     ctx->stats = mdb_stats{};
     ctx->counter_base = 0;
@@ -2006,8 +2000,8 @@ static mdb_status hnsw_ann_search_impl(mdb_hnsw* h, const float* queries, size_t
     if (mem == MDB_MEM_DEVICE)
         return fuse.done ? MDB_OK : s.remap((uint64_t*)keys, (uint32_t*)cnts, b, k, nullptr, doc_ids_out, scores_out, counts_out);
     void *dids, *dsc;
-    MDB_TRY(mdb_scratch(ctx, 5, total * 16 + 16, &dids));
-    MDB_TRY(mdb_scratch(ctx, 1, total * 4 + 16, &dsc));
+    MDB_TRY(mdb_scratch(ctx, total * 16 + 16, &dids));
+    MDB_TRY(mdb_scratch(ctx, total * 4 + 16, &dsc));
     MDB_TRY(s.remap((uint64_t*)keys, (uint32_t*)cnts, b, k, nullptr, (mdb_u128*)dids, (float*)dsc, nullptr));
     const HostCopy back[3] = {{doc_ids_out, dids, total * 16}, {scores_out, dsc, total * 4}, {counts_out, cnts, b * 4}};
     return mdb_return_to_host(ctx, back, 3);

@@ -53,8 +53,7 @@ extern "C" mdb_status mdb_hnsw_select_neighbors(mdb_ctx* ctx, const float* vecto
                                                 const uint32_t* cand_ids, const float* cand_dist, size_t rows, size_t width,
                                                 size_t max_neighbors, uint32_t* ids_out, float* dist_out, uint32_t* counts_out) {
     if (!ctx || !vectors || (!cand_ids && rows) || (!cand_dist && rows) || !ids_out || !dist_out || !counts_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (max_neighbors == 0 || max_neighbors > 64) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "max_neighbors must be 1..64 (one lane per kept neighbour)");
     if (rows == 0 || width == 0) return MDB_OK;
     for (size_t i = 0; i < rows * width; ++i)
@@ -62,16 +61,16 @@ extern "C" mdb_status mdb_hnsw_select_neighbors(mdb_ctx* ctx, const float* vecto
     const float* dv = vectors;
     if (vectors_mem == MDB_MEM_HOST) {
         void* p;
-        MDB_TRY(mdb_scratch(ctx, 0, n * d * 4 + 64, &p));
+        MDB_TRY(mdb_scratch(ctx, n * d * 4 + 64, &p));
         MDB_HIP(ctx, hipMemcpyAsync(p, vectors, n * d * 4, hipMemcpyHostToDevice, ctx->stream));
         dv = (const float*)p;
     }
     void *dc, *dd, *oi, *od, *oc;
-    MDB_TRY(mdb_scratch(ctx, 1, rows * width * 4, &dc));
-    MDB_TRY(mdb_scratch(ctx, 2, rows * width * 4, &dd));
-    MDB_TRY(mdb_scratch(ctx, 3, rows * max_neighbors * 4, &oi));
-    MDB_TRY(mdb_scratch(ctx, 4, rows * max_neighbors * 4, &od));
-    MDB_TRY(mdb_scratch(ctx, 5, rows * 4, &oc));
+    MDB_TRY(mdb_scratch(ctx, rows * width * 4, &dc));
+    MDB_TRY(mdb_scratch(ctx, rows * width * 4, &dd));
+    MDB_TRY(mdb_scratch(ctx, rows * max_neighbors * 4, &oi));
+    MDB_TRY(mdb_scratch(ctx, rows * max_neighbors * 4, &od));
+    MDB_TRY(mdb_scratch(ctx, rows * 4, &oc));
     MDB_HIP(ctx, hipMemcpyAsync(dc, cand_ids, rows * width * 4, hipMemcpyHostToDevice, ctx->stream));
     MDB_HIP(ctx, hipMemcpyAsync(dd, cand_dist, rows * width * 4, hipMemcpyHostToDevice, ctx->stream));
     const DistPlan p = make_plan((int)d, metric);

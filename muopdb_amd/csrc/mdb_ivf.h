@@ -137,6 +137,8 @@ struct IvfSet {
                             uint32_t* d_doc_counts);
     // exact list-sharded search: keys -> one rank's points block; `world` blocks -> merged rows
     mdb_status pack_points(const uint64_t* d_keys, const uint32_t* d_counts, const uint8_t* d_found, size_t b, size_t k, void* d_block);
+    // the same into a caller's host block, through scratch; the block's pad bytes, which the kernel leaves alone, arrive as zeros
+    mdb_status pack_points_to_host(const uint64_t* d_keys, const uint32_t* d_counts, const uint8_t* d_found, size_t b, size_t k, void* h_block);
     mdb_status merge_points(const void* d_blocks, size_t world, size_t b, size_t k, const uint32_t* d_q_user, mdb_u128* d_doc,
                             float* d_score, uint32_t* d_counts_out, uint8_t* d_found_out);
     // algorithmic bytes per scored vector

@@ -379,9 +379,9 @@ mdb_status IvfSet::stage_filter(const uint32_t* allow, size_t n_bitmaps, size_t 
     if (mem == MDB_MEM_DEVICE) { out->allow = allow; return MDB_OK; }
     const size_t bytes = n_bitmaps * words * 4;
     void *pin, *dev;
-    MDB_TRY(mdb_pinned(ctx, 2, bytes, &pin));
+    MDB_TRY(mdb_pinned(ctx, MDB_PIN_FILTER, bytes, &pin));
     memcpy(pin, allow, bytes);
-    MDB_TRY(mdb_scratch(ctx, 15, bytes, &dev));   // a slot of its own: the coarse search of a large index uses 8-10, 12 (flat_topk_keys_mfma)
+    MDB_TRY(mdb_scratch(ctx, bytes, &dev));
     MDB_HIP(ctx, hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, ctx->stream));
     out->allow = (const uint32_t*)dev;
     return MDB_OK;
@@ -451,7 +451,7 @@ mdb_status IvfSet::scan(const float* d_q, int qstride, size_t b, const uint32_t*
     // one block per query: its sorted keys ARE the result — written in place, no merge launch
     const bool direct = nsplit == 1 && k > 0;
     void* partial = d_keys;
-    if (!direct) MDB_TRY(mdb_scratch(ctx, 4, b * (size_t)nsplit * std::max<size_t>(k, 1) * 8, &partial));
+    if (!direct) MDB_TRY(mdb_scratch(ctx, b * (size_t)nsplit * std::max<size_t>(k, 1) * 8, &partial));
     ScanArgs a{d_users.p, d_q_user, d_list_tile_off.p, d_slot_ids.p, d_tomb.p, d_probes, d_probe_cnt, probe_stride,
                (int)k, (uint64_t*)partial, ctx->d_flags, ctx->d_counters,
                sm.allow, sm.allow_stride, sm.allow_mask,
@@ -461,7 +461,7 @@ mdb_status IvfSet::scan(const float* d_q, int qstride, size_t b, const uint32_t*
     size_t sel_lds = BlockSelect<MDB_BLOCK>::lds_bytes((int)k);
     void* qcodes = nullptr;
     if (kind == MDB_QUANT_PQ) {
-        MDB_TRY(mdb_scratch(ctx, 7, b * (size_t)pq.m + 16, &qcodes));
+        MDB_TRY(mdb_scratch(ctx, b * (size_t)pq.m + 16, &qcodes));
         MDB_TRY(pq_quantize_device(ctx, pq, d_q, b, (uint8_t*)qcodes, qstride));  // Q::QuantizedT::process_vector, index.rs:193
     }
     {
@@ -483,8 +483,8 @@ mdb_status IvfSet::scan(const float* d_q, int qstride, size_t b, const uint32_t*
             const int ns3 = (int)std::min<size_t>(std::max<size_t>((tgt3 + b - 1) / b, 1), std::min<size_t>(16, (size_t)std::max(probe_stride, 1)));
             const uint32_t cap3 = (uint32_t)std::max<long long>(1, ctx->opt.pq3_cap);   // (tests force the overflow path)
             uint32_t *cand, *ccnt;
-            MDB_TRY(mdb_scratch(ctx, 13, b * (size_t)ns3 * cap3 * 4 * (1 + (size_t)mw), (void**)&cand));
-            MDB_TRY(mdb_scratch(ctx, 14, b * (size_t)ns3 * 4 + 512, (void**)&ccnt));
+            MDB_TRY(mdb_scratch(ctx, b * (size_t)ns3 * cap3 * 4 * (1 + (size_t)mw), (void**)&cand));
+            MDB_TRY(mdb_scratch(ctx, b * (size_t)ns3 * 4 + 512, (void**)&ccnt));
             uint32_t* ovf3 = ccnt + ((b * (size_t)ns3 + 63) / 64) * 64;   // own 256-byte line
             MDB_HIP(ctx, hipMemsetAsync(ovf3, 0, 4, ctx->stream));
             const Pq3Args c3{cand, ccnt, cap3, ovf3};
@@ -623,7 +623,7 @@ mdb_status IvfSet::search_fused(const float* d_q, int qstride, size_t b, const u
     if (coarse_mode == 2 && ctx->opt.cm_split) {
         // the coarse search as its own two launches (filter + one small block per query: ivf_coarse_rank_kernel), the fused kernel takes the probes
         void* pr;
-        MDB_TRY(mdb_scratch(ctx, 2, b * num_probes * 4, &pr));
+        MDB_TRY(mdb_scratch(ctx, b * num_probes * 4, &pr));
         MDB_TRY(cm_find_nearest(ctx, cmf, (const float4*)(d_cent_tiles.p + (size_t)h_users[0].cent_tile_base * MDB_TILE * d4 * 4), make_plan((int)num_features, MDB_METRIC_L2),
                                 d_q, qstride, b, num_probes, (uint32_t*)pr, nullptr));
         a.probes = (const uint32_t*)pr;
@@ -631,13 +631,13 @@ mdb_status IvfSet::search_fused(const float* d_q, int qstride, size_t b, const u
     }
     fa.coarse_blocks = coarse_mode == 1 ? fa.tile_groups * (uint32_t)((b + PQF_QT - 1) / PQF_QT) : 0u;
     void *cdist = nullptr, *qcodes;
-    if (coarse_mode == 1) MDB_TRY(mdb_scratch(ctx, 4, b * (size_t)fa.cent_ntiles * MDB_TILE * 4, &cdist));
+    if (coarse_mode == 1) MDB_TRY(mdb_scratch(ctx, b * (size_t)fa.cent_ntiles * MDB_TILE * 4, &cdist));
     CoarseShape csh{};
     if (coarse_mode == 2) {
         csh = cm_shape(cmf, b, num_probes, (uint32_t)PQF_CAP);
         void *cand, *ccnt;
-        MDB_TRY(mdb_scratch(ctx, 4, b * (size_t)csh.S * csh.caps * 8, &cand));
-        MDB_TRY(mdb_scratch(ctx, 13, b * (size_t)(csh.S + 1) * 4 + 16, &ccnt));
+        MDB_TRY(mdb_scratch(ctx, b * (size_t)csh.S * csh.caps * 8, &cand));
+        MDB_TRY(mdb_scratch(ctx, b * (size_t)(csh.S + 1) * 4 + 16, &ccnt));
         fa.cm_global = ctx->opt.cm_global_bound ? 1u : 0u;
         fa.cm_kappa = cmf.kappa;
         fa.cm_xnmax = cmf.xnmax;
@@ -647,12 +647,12 @@ mdb_status IvfSet::search_fused(const float* d_q, int qstride, size_t b, const u
         fa.cm_S = csh.S;
         fa.cm_caps = csh.caps;
     }
-    MDB_TRY(mdb_scratch(ctx, 7, b * (size_t)pq.m + 16, &qcodes));
+    MDB_TRY(mdb_scratch(ctx, b * (size_t)pq.m + 16, &qcodes));
     fa.cdist = (float*)cdist;
     fa.qcodes = (uint8_t*)qcodes;
     if (ctx->opt.pqf_dbg) {
         void* dbg;
-        MDB_TRY(mdb_scratch(ctx, 12, 256, &dbg));
+        MDB_TRY(mdb_scratch(ctx, 256, &dbg));
         MDB_HIP(ctx, hipMemsetAsync(dbg, 0, 256, ctx->stream));
         fa.dbg = (unsigned long long*)dbg;
     }
@@ -728,6 +728,16 @@ mdb_status IvfSet::pack_points(const uint64_t* d_keys, const uint32_t* d_counts,
     return MDB_OK;
 }
 
+mdb_status IvfSet::pack_points_to_host(const uint64_t* d_keys, const uint32_t* d_counts, const uint8_t* d_found, size_t b, size_t k, void* h_block) {
+    const size_t nb = mdb_points_block_bytes_impl(b, k), used = b * k * 8 + b * 5;
+    void* dblk;
+    MDB_TRY(mdb_scratch(ctx, nb, &dblk));
+    if (nb > used) MDB_HIP(ctx, hipMemsetAsync((char*)dblk + used, 0, nb - used, ctx->stream));
+    MDB_TRY(pack_points(d_keys, d_counts, d_found, b, k, dblk));
+    const HostCopy back[1] = {{h_block, dblk, nb}};
+    return mdb_return_to_host(ctx, back, 1);
+}
+
 mdb_status IvfSet::merge_points(const void* d_blocks, size_t world, size_t b, size_t k, const uint32_t* d_q_user, mdb_u128* d_doc,
                                 float* d_score, uint32_t* d_counts_out, uint8_t* d_found_out) {
     if (b == 0) return MDB_OK;
@@ -759,7 +769,7 @@ mdb_status IvfSet::coarse(size_t ui, const float* d_q, int qstride, size_t b, si
     TileView cv{d_cent_tiles.p + (size_t)h_users[ui].cent_tile_base * MDB_TILE * d4 * 4, bi.num_clusters,
                 (bi.num_clusters + MDB_TILE - 1) / MDB_TILE, (int)num_features, d4};
     void* keys;
-    MDB_TRY(mdb_scratch(ctx, 5, b * num_probes * 8, &keys));
+    MDB_TRY(mdb_scratch(ctx, b * num_probes * 8, &keys));
     if (ui == 0 && cm_usable(cmf, ctx, d_q, qstride, b, num_probes)) {
         // mid-sized coarse quantizer of one L2 PQ index: matrix-core filter + exact candidates (mdb_ivf_coarse.hip.h), the same ids
         return cm_find_nearest(ctx, cmf, (const float4*)cv.data, make_plan((int)num_features, MDB_METRIC_L2), d_q, qstride, b, num_probes, d_probes,
@@ -806,17 +816,12 @@ static mdb_status ivf_search_impl(mdb_ivf* ivf, const float* queries, size_t b, 
                                   const FilterArg* fa = nullptr, bool submit = false) {
     IvfSet& s = ivf->set;
     mdb_ctx* ctx = s.ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     MDB_TRY(mdb_require_idle(ctx, mem));
     const bool remap = mode == OUT_DOCS;
     if (b == 0) return MDB_OK;
     if (k > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
-    struct SubmitScope {  // mdb_*_search_submit: mdb_return_to_host enqueues instead of synchronising
-        mdb_ctx* c; bool on;
-        SubmitScope(mdb_ctx* c_, bool on_) : c(c_), on(on_) { if (on) c->submit_mode = true; }
-        ~SubmitScope() { if (on) c->submit_mode = false; }
-    } submit_scope(ctx, submit && mem == MDB_MEM_HOST);
+    SubmitScope submit_scope(ctx, submit && mem == MDB_MEM_HOST);
     IvfSet::ScanFilter filt;
     if (fa) MDB_TRY(s.stage_filter(fa->allow, fa->n_bitmaps, fa->words, mem, b, &filt));
     float* dq;
@@ -825,14 +830,14 @@ static mdb_status ivf_search_impl(mdb_ivf* ivf, const float* queries, size_t b, 
     // small batches of an L2 PQ index: the whole step is ONE kernel (ivf_pq_fused_kernel), device-resident queries are read in place
     const bool fused = s.fused_ok(b, k, num_probes, probes != nullptr);
     if (fused && mem == MDB_MEM_DEVICE) { dq = const_cast<float*>(queries); qstride = (int)s.num_features; }
-    else MDB_TRY(stage_queries(ctx, 0, queries, b, (int)s.num_features, mem, bpad, &dq, &qstride));
+    else MDB_TRY(stage_queries(ctx, queries, b, (int)s.num_features, mem, bpad, &dq, &qstride));
     void* dprobes;
-    MDB_TRY(mdb_scratch(ctx, 2, b * std::max<size_t>(num_probes, 1) * 4, &dprobes));
+    MDB_TRY(mdb_scratch(ctx, b * std::max<size_t>(num_probes, 1) * 4, &dprobes));
     if (probes) {
         if (num_probes == 0) { /* empty centroid list: empty results */ }
         else if (mem == MDB_MEM_HOST) {  // through pinned staging: the caller's buffer is free when the call returns
             void* pin;
-            MDB_TRY(mdb_pinned(ctx, 3, b * num_probes * 4, &pin));
+            MDB_TRY(mdb_pinned(ctx, MDB_PIN_AUX, b * num_probes * 4, &pin));
             memcpy(pin, probes, b * num_probes * 4);
             MDB_HIP(ctx, hipMemcpyAsync(dprobes, pin, b * num_probes * 4, hipMemcpyHostToDevice, ctx->stream));
         } else MDB_HIP(ctx, hipMemcpyAsync(dprobes, probes, b * num_probes * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -840,8 +845,8 @@ static mdb_status ivf_search_impl(mdb_ivf* ivf, const float* queries, size_t b, 
         MDB_TRY(s.coarse(0, dq, qstride, b, num_probes, (uint32_t*)dprobes, true, bpad));  // also clears the device counters
     }
     void *keys, *cnts;
-    MDB_TRY(mdb_scratch(ctx, 3, b * std::max<size_t>(k, 1) * 8, &keys));
-    MDB_TRY(mdb_scratch(ctx, 6, b * 4 + 16, &cnts));
+    MDB_TRY(mdb_scratch(ctx, b * std::max<size_t>(k, 1) * 8, &keys));
+    MDB_TRY(mdb_scratch(ctx, b * 4 + 16, &cnts));
     if (probes && !fused) MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 32, ctx->stream));
     ctx->dev_counters = true;
     ctx->stats = mdb_stats{};
@@ -857,8 +862,8 @@ static mdb_status ivf_search_impl(mdb_ivf* ivf, const float* queries, size_t b, 
             return s.search_fused(dq, qstride, b, fp, num_probes, k, &filt, nullptr, nullptr, (mdb_u128*)ids_out, scores_out, counts_out);
         } else {
             void *dids, *dsc;
-            MDB_TRY(mdb_scratch(ctx, 5, total * 16 + 16, &dids));
-            MDB_TRY(mdb_scratch(ctx, 1, total * 4 + 16, &dsc));
+            MDB_TRY(mdb_scratch(ctx, total * 16 + 16, &dids));
+            MDB_TRY(mdb_scratch(ctx, total * 4 + 16, &dsc));
             MDB_TRY(s.search_fused(dq, qstride, b, fp, num_probes, k, &filt, nullptr, nullptr, (mdb_u128*)dids, (float*)dsc, (uint32_t*)cnts));
             const HostCopy back[3] = {{ids_out, dids, total * 16}, {scores_out, dsc, total * 4}, {counts_out, cnts, b * 4}};
             return mdb_return_to_host(ctx, back, 3);
@@ -867,12 +872,7 @@ static mdb_status ivf_search_impl(mdb_ivf* ivf, const float* queries, size_t b, 
     MDB_TRY(s.scan(dq, qstride, b, nullptr, (uint32_t*)dprobes, nullptr, (int)num_probes, k, (uint64_t*)keys, (uint32_t*)cnts, &filt));
     if (mode == OUT_BLOCK) {
         if (mem == MDB_MEM_DEVICE) return s.pack_points((uint64_t*)keys, (uint32_t*)cnts, nullptr, b, k, ids_out);
-        void* dblk;
-        const size_t nb = mdb_points_block_bytes_impl(b, k);
-        MDB_TRY(mdb_scratch(ctx, 5, nb, &dblk));
-        MDB_TRY(s.pack_points((uint64_t*)keys, (uint32_t*)cnts, nullptr, b, k, dblk));
-        const HostCopy back[1] = {{ids_out, dblk, nb}};
-        return mdb_return_to_host(ctx, back, 1);
+        return s.pack_points_to_host((uint64_t*)keys, (uint32_t*)cnts, nullptr, b, k, ids_out);
     }
     if (mem == MDB_MEM_DEVICE) {
         if (remap) MDB_TRY(s.remap((uint64_t*)keys, (uint32_t*)cnts, b, k, nullptr, (mdb_u128*)ids_out, scores_out, counts_out));
@@ -883,8 +883,8 @@ static mdb_status ivf_search_impl(mdb_ivf* ivf, const float* queries, size_t b, 
         return MDB_OK;
     }
     void *dids, *dsc;
-    MDB_TRY(mdb_scratch(ctx, 5, total * 16 + 16, &dids));
-    MDB_TRY(mdb_scratch(ctx, 1, total * 4 + 16, &dsc));
+    MDB_TRY(mdb_scratch(ctx, total * 16 + 16, &dids));
+    MDB_TRY(mdb_scratch(ctx, total * 4 + 16, &dsc));
     if (remap) MDB_TRY(s.remap((uint64_t*)keys, (uint32_t*)cnts, b, k, nullptr, (mdb_u128*)dids, (float*)dsc, nullptr));
     else if (total) unpack_keys(ctx, (uint64_t*)keys, total, (uint32_t*)dids, (float*)dsc);
     const HostCopy back[3] = {{ids_out, dids, total * (remap ? 16 : 4)}, {scores_out, dsc, total * 4}, {counts_out, cnts, b * 4}};
@@ -898,8 +898,7 @@ mdb_status mdb_ivf_load(mdb_ctx* ctx, const void* index_bytes, size_t index_len,
                         uint32_t shard_rank, uint32_t shard_world, mdb_ivf** out) {
     if (!ctx || !index_bytes || !vectors_bytes || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     mdb_ivf* ivf = new mdb_ivf();
     mdb_status st = ivf->set.load(ctx, (const uint8_t*)index_bytes, index_len, (const uint8_t*)vectors_bytes, vectors_len,
                                   {{index_offset, vectors_offset}}, quant, shard_rank, shard_world);
@@ -940,18 +939,17 @@ mdb_status mdb_ivf_find_nearest_centroids(mdb_ivf* ivf, const float* queries, si
     if (!ivf || (!queries && b) || !out) return MDB_ERR_INVALID_ARG;
     IvfSet& s = ivf->set;
     mdb_ctx* ctx = s.ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (num_probes == 0 || num_probes > s.blobs[0].num_clusters)
         return mdb_fail(ctx, MDB_ERR_OUT_OF_RANGE, "num_probes=%zu out of range (num_clusters=%u)", num_probes, s.blobs[0].num_clusters);
     if (b == 0) return MDB_OK;
     float* dq;
     int qstride;
     const size_t bpad = s.coarse_bpad(b);
-    MDB_TRY(stage_queries(ctx, 0, queries, b, (int)s.num_features, mem, bpad, &dq, &qstride));
+    MDB_TRY(stage_queries(ctx, queries, b, (int)s.num_features, mem, bpad, &dq, &qstride));
     if (mem == MDB_MEM_DEVICE) return s.coarse(0, dq, qstride, b, num_probes, out, false, bpad);
     void* dprobes;
-    MDB_TRY(mdb_scratch(ctx, 2, b * num_probes * 4, &dprobes));
+    MDB_TRY(mdb_scratch(ctx, b * num_probes * 4, &dprobes));
     MDB_TRY(s.coarse(0, dq, qstride, b, num_probes, (uint32_t*)dprobes, false, bpad));
     MDB_HIP(ctx, hipMemcpyAsync(out, dprobes, b * num_probes * 4, hipMemcpyDeviceToHost, ctx->stream));
     return mdb_check_flags(ctx);
@@ -967,15 +965,14 @@ mdb_status mdb_ivf_coarse_keys(mdb_ivf* ivf, const float* queries, size_t b, siz
     if (!ivf || (!queries && b) || !keys_out) return MDB_ERR_INVALID_ARG;
     IvfSet& s = ivf->set;
     mdb_ctx* ctx = s.ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     const size_t L = s.blobs[0].num_clusters;
     if (num_probes == 0 || num_probes > MDB_MAX_K || (first % MDB_TILE) != 0 || first > L || count > L - first)
         return mdb_fail(ctx, MDB_ERR_OUT_OF_RANGE, "coarse_keys: num_probes=%zu, centroid range [%zu, %zu) of %zu", num_probes, first, first + count, L);
     if (b == 0) return MDB_OK;
     const size_t total = b * num_probes;
     void* dkeys = keys_out;
-    if (mem == MDB_MEM_HOST) MDB_TRY(mdb_scratch(ctx, 5, total * 8, &dkeys));
+    if (mem == MDB_MEM_HOST) MDB_TRY(mdb_scratch(ctx, total * 8, &dkeys));
     if (count == 0) {
         MDB_HIP(ctx, hipMemsetAsync(dkeys, 0xFF, total * 8, ctx->stream));
     } else {
@@ -995,7 +992,7 @@ mdb_status mdb_ivf_coarse_keys(mdb_ivf* ivf, const float* queries, size_t b, siz
             batched = s.slice_first == first && flat_mfma_applicable(ctx, cv, s.cent_slice, b, num_probes);
         }
         const size_t bpad = batched ? (b + 255) / 256 * 256 : (b + 3) / 4 * 4;
-        MDB_TRY(stage_queries(ctx, 0, queries, b, (int)s.num_features, mem, bpad, &dq, &qstride));
+        MDB_TRY(stage_queries(ctx, queries, b, (int)s.num_features, mem, bpad, &dq, &qstride));
         if (batched) MDB_TRY(flat_topk_keys_mfma(ctx, cv, s.cent_slice, MDB_METRIC_L2, dq, qstride, b, bpad, num_probes, (uint64_t*)dkeys, nullptr));
         else MDB_TRY(flat_topk_keys(ctx, cv, MDB_METRIC_L2, dq, qstride, b, num_probes, (uint64_t*)dkeys, nullptr));
         if (first) keys_add_id_offset_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, ctx->stream>>>((uint64_t*)dkeys, total, (uint32_t)first);
@@ -1010,8 +1007,7 @@ mdb_status mdb_ivf_merge_coarse_keys(mdb_ivf* ivf, const uint64_t* keys, size_t 
                                      uint32_t* probes_out) {
     if (!ivf || (!keys && b) || !probes_out || parts == 0 || num_probes == 0) return MDB_ERR_INVALID_ARG;
     mdb_ctx* ctx = ivf->set.ctx;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (num_probes > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "num_probes=%zu exceeds MDB_MAX_K=%d", num_probes, MDB_MAX_K);
     if (b == 0) return MDB_OK;
     const size_t per = parts * num_probes, total = b * num_probes;
@@ -1019,18 +1015,18 @@ mdb_status mdb_ivf_merge_coarse_keys(mdb_ivf* ivf, const uint64_t* keys, size_t 
     void *stage, *merged, *dist, *dids = probes_out;
     if (mem == MDB_MEM_HOST) {
         void* pin;
-        MDB_TRY(mdb_pinned(ctx, 0, b * per * 8, &pin));
+        MDB_TRY(mdb_pinned(ctx, MDB_PIN_IN, b * per * 8, &pin));
         memcpy(pin, keys, b * per * 8);
-        MDB_TRY(mdb_scratch(ctx, 4, b * per * 8, &stage));
+        MDB_TRY(mdb_scratch(ctx, b * per * 8, &stage));
         MDB_HIP(ctx, hipMemcpyAsync(stage, pin, b * per * 8, hipMemcpyHostToDevice, ctx->stream));
         din = (const uint64_t*)stage;
-        MDB_TRY(mdb_scratch(ctx, 2, total * 4, &dids));
+        MDB_TRY(mdb_scratch(ctx, total * 4, &dids));
     }
     if (per * 8 <= 48 * 1024) {
         MDB_TRY(merge_sorted_rows(ctx, din, parts, num_probes, b, nullptr, nullptr, (uint32_t*)dids, nullptr));
     } else {
-        MDB_TRY(mdb_scratch(ctx, 5, total * 8, &merged));
-        MDB_TRY(mdb_scratch(ctx, 1, total * 4 + 16, &dist));
+        MDB_TRY(mdb_scratch(ctx, total * 8, &merged));
+        MDB_TRY(mdb_scratch(ctx, total * 4 + 16, &dist));
         MDB_TRY(merge_keys(ctx, din, per, b, num_probes, (uint64_t*)merged, nullptr));
         MDB_TRY(unpack_keys(ctx, (const uint64_t*)merged, total, (uint32_t*)dids, (float*)dist));
     }
@@ -1091,8 +1087,7 @@ mdb_status mdb_ivf_merge_shards(mdb_ivf* ivf, const void* blocks, size_t world, 
                                 float* scores_out, uint32_t* counts_out) {
     if (!ivf || !blocks || !doc_ids_out || !scores_out || world == 0) return MDB_ERR_INVALID_ARG;
     IvfSet& s = ivf->set;
-    std::lock_guard<std::mutex> g(s.ctx->mu);
-    MDB_HIP(s.ctx, hipSetDevice(s.ctx->device));
+    MDB_ENTER(s.ctx);
     if (k > MDB_MAX_K) return mdb_fail(s.ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
     return s.merge_points(blocks, world, b, k, nullptr, doc_ids_out, scores_out, counts_out, nullptr);
 }
@@ -1100,15 +1095,13 @@ mdb_status mdb_ivf_merge_shards(mdb_ivf* ivf, const void* blocks, size_t world, 
 
 mdb_status mdb_ivf_invalidate(mdb_ivf* ivf, const mdb_u128* doc_ids, size_t n, uint8_t* flags_out) {
     if (!ivf || (!doc_ids && n) || !flags_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ivf->set.ctx->mu);
-    MDB_HIP(ivf->set.ctx, hipSetDevice(ivf->set.ctx->device));
+    MDB_ENTER(ivf->set.ctx);
     return ivf->set.invalidate(0, doc_ids, n, flags_out, false);
 }
 
 mdb_status mdb_ivf_is_invalidated(mdb_ivf* ivf, const mdb_u128* doc_ids, size_t n, uint8_t* flags_out) {
     if (!ivf || (!doc_ids && n) || !flags_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ivf->set.ctx->mu);
-    MDB_HIP(ivf->set.ctx, hipSetDevice(ivf->set.ctx->device));
+    MDB_ENTER(ivf->set.ctx);
     return ivf->set.invalidate(0, doc_ids, n, flags_out, true);
 }
 

@@ -704,7 +704,7 @@ static mdb_status cm_launch(mdb_ctx* ctx, const CoarseMfma& cm, const float* d_q
     const unsigned qblocks = cq.qcodes ? (unsigned)((b * (size_t)cq.m + CM_NW - 1) / CM_NW) : 0u;
     if (ctx->opt.cm_dbg) {
         void* dbg;
-        MDB_TRY(mdb_scratch(ctx, 12, 256, &dbg));
+        MDB_TRY(mdb_scratch(ctx, 256, &dbg));
         MDB_HIP(ctx, hipMemsetAsync(dbg, 0, 256, ctx->stream));
         a.dbg = (unsigned long long*)dbg;
     }
@@ -744,8 +744,8 @@ static mdb_status cm_find_nearest(mdb_ctx* ctx, const CoarseMfma& cm, const floa
                                   size_t P, uint32_t* d_probes, unsigned long long* zero4) {
     const CoarseShape sh = cm_shape(cm, b, P, CMR_CAP);
     void *cand, *ccnt;
-    MDB_TRY(mdb_scratch(ctx, 4, b * (size_t)sh.S * sh.caps * 8, &cand));
-    MDB_TRY(mdb_scratch(ctx, 13, b * (size_t)(sh.S + 1) * 4 + 16, &ccnt));
+    MDB_TRY(mdb_scratch(ctx, b * (size_t)sh.S * sh.caps * 8, &cand));
+    MDB_TRY(mdb_scratch(ctx, b * (size_t)(sh.S + 1) * 4 + 16, &ccnt));
     MDB_TRY(cm_launch(ctx, cm, d_q, qstride, b, P, sh, (uint2*)cand, (uint32_t*)ccnt));
     const CmSelect cs{(const uint2*)cand, (const uint32_t*)ccnt, cm.rows.p, cent_tiles, sh.S, sh.caps, cm.n, (uint32_t)b, cm.kappa, cm.xnmax, cp, ctx->opt.cm_global_bound ? 1u : 0u};
     const size_t lds = CMR_CAP * 8 + (36 + 4 + 64 + 2 * 16 * CM_PRE + 4 * (size_t)cp.d4) * 4 + ((BlockSelect<256>::lds_bytes((int)P) + 15) & ~(size_t)15);

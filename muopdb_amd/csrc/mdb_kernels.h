@@ -10,8 +10,8 @@ mdb_status pq_quantize_device(mdb_ctx* ctx, const PqDev& pq, const float* d_vecs
 // ---- mdb_flat.hip
 // row-major rows (device, any alignment) -> list-contiguous SoA tiles
 mdb_status tiles_from_rows(mdb_ctx* ctx, const float* d_rows, size_t n, int d, TileStore& out);
-// pad queries [b][d] (host or device) into scratch slot `slot` as [bpad][d4*4] zero-filled device rows
-mdb_status stage_queries(mdb_ctx* ctx, int slot, const float* queries, size_t b, int d, mdb_mem mem, size_t bpad,
+// pad queries [b][d] (host or device) into the call's scratch as [bpad][d4*4] zero-filled device rows
+mdb_status stage_queries(mdb_ctx* ctx, const float* queries, size_t b, int d, mdb_mem mem, size_t bpad,
                          float** d_out, int* qstride);
 // flat exact top-k of every query against a TileStore: keys (distance,row) ascending into d_keys [b][k]
 // gate (device word, optional): both launches return immediately while *gate == 0

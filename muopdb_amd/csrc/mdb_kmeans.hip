@@ -165,8 +165,7 @@ extern "C" mdb_status mdb_kmeans_fit(mdb_ctx* ctx, const float* data, size_t n, 
                                      float tolerance, const uint64_t* init_point_ids, size_t n_init, mdb_mem mem,
                                      float* centroids_out, uint32_t* assignments_out, float* error_out, uint32_t* iterations_out) {
     if (!ctx || !data || !init_point_ids || !centroids_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     const size_t k = std::min(num_clusters, n);
     if (k == 0 || d == 0) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "k-means over an empty data set");
     if (n_init != k) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "init_point_ids must hold min(num_clusters, n) = %zu point ids (got %zu)", k, n_init);

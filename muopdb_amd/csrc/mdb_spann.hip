@@ -104,42 +104,32 @@ static mdb_status spann_search_impl(SpannSet& s, const float* queries, size_t b,
     mdb_ctx* ctx = s.ctx;
     MDB_TRY(mdb_require_idle(ctx, mem));
     if (b == 0) return MDB_OK;
-    struct SubmitScope {  // mdb_*_search_submit: mdb_return_to_host enqueues instead of synchronising
-        mdb_ctx* c; bool on;
-        SubmitScope(mdb_ctx* c_, bool on_) : c(c_), on(on_) { if (on) c->submit_mode = true; }
-        ~SubmitScope() { if (on) c->submit_mode = false; }
-    } submit_scope(ctx, submit && mem == MDB_MEM_HOST);
+    SubmitScope submit_scope(ctx, submit && mem == MDB_MEM_HOST);
     const size_t k = params->top_k;
     const size_t nexp = params->num_explored_centroids < 0 ? k : (size_t)params->num_explored_centroids;
     if (k > MDB_MAX_K || nexp > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "top_k / num_explored_centroids exceed MDB_MAX_K=%d", MDB_MAX_K);
     float* dq;
     int qstride;
-    MDB_TRY(stage_queries(ctx, 0, queries, b, (int)s.ivf.num_features, mem, (b + 3) / 4 * 4, &dq, &qstride));
-    // all per-call device buffers come from ONE grow-only scratch slot: no hipMalloc / hipFree (which would
-    // synchronise the device) on the search path
+    MDB_TRY(stage_queries(ctx, queries, b, (int)s.ivf.num_features, mem, (b + 3) / 4 * 4, &dq, &qstride));
     const size_t ne = std::max<size_t>(nexp, 1), ke = std::max<size_t>(k, 1), total = b * k;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-    const size_t o_qu = take(b * 4), o_ckeys = take(b * ne * 8), o_ccnt = take(b * 4), o_probes = take(b * ne * 4), o_pcnt = take(b * 4),
-                 o_keys = take(b * ke * 8), o_cnts = take(b * 4), o_found = take(b), o_doc = take(b * ke * 16), o_sc = take(b * ke * 4),
-                 o_blk = take(block_out ? mdb_points_block_bytes_impl(b, k) : 0), o_rows = take(pio ? b * (ne + 2) * 4 : 0);
-    char* base;
-    MDB_TRY(mdb_scratch(ctx, 11, off, (void**)&base));
+    uint64_t *ckeys, *keys;
+    uint32_t *ccnt, *probes, *pcnt, *cnts;
+    uint8_t* dfound;
+    MDB_TRY(mdb_scratch(ctx, b * ne * 8, (void**)&ckeys));
+    MDB_TRY(mdb_scratch(ctx, b * 4, (void**)&ccnt));
+    MDB_TRY(mdb_scratch(ctx, b * ne * 4, (void**)&probes));
+    MDB_TRY(mdb_scratch(ctx, b * 4, (void**)&pcnt));
+    MDB_TRY(mdb_scratch(ctx, b * ke * 8, (void**)&keys));
+    MDB_TRY(mdb_scratch(ctx, b * 4, (void**)&cnts));
+    MDB_TRY(mdb_scratch(ctx, b, (void**)&dfound));
     uint32_t* d_q_user = nullptr;
     if (h_q_user) {  // through event-guarded pinned staging: the caller's (stack) array may die before the copy runs, and a
                      // MDB_MEM_DEVICE call returns without a sync, so the next call must not overwrite a buffer still being read
-        MDB_TRY(mdb_stage_small(ctx, h_q_user, b * 4, base + o_qu));
-        d_q_user = (uint32_t*)(base + o_qu);
+        MDB_TRY(mdb_scratch(ctx, b * 4, (void**)&d_q_user));
+        MDB_TRY(mdb_stage_small(ctx, h_q_user, b * 4, d_q_user));
     }
     IvfSet::ScanFilter filt;
     if (fa) MDB_TRY(s.ivf.stage_filter(fa->allow, fa->n_bitmaps, fa->words, mem, b, &filt, h_q_user));
-    uint64_t* ckeys = (uint64_t*)(base + o_ckeys);
-    uint32_t* ccnt = (uint32_t*)(base + o_ccnt);
-    uint32_t* probes = (uint32_t*)(base + o_probes);
-    uint32_t* pcnt = (uint32_t*)(base + o_pcnt);
-    uint64_t* keys = (uint64_t*)(base + o_keys);
-    uint32_t* cnts = (uint32_t*)(base + o_cnts);
-    uint8_t* dfound = (uint8_t*)(base + o_found);
     // (a device call whose merge launch saved and cleared the counters — ScanRemap::save_counters — leaves them clean for the next one)
     if (!ctx->counters_clean) MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 32, ctx->stream));
     ctx->counters_clean = false;
@@ -156,7 +146,7 @@ static mdb_status spann_search_impl(SpannSet& s, const float* queries, size_t b,
         // ---- probes as given: the centroid-graph search ran elsewhere (another rank, for its slice of the batch)
         uint32_t* rows = pio->rows;
         if (mem != MDB_MEM_DEVICE) {
-            rows = (uint32_t*)(base + o_rows);
+            MDB_TRY(mdb_scratch(ctx, b * prow * 4, (void**)&rows));
             MDB_TRY(mdb_stage_small(ctx, pio->rows, b * prow * 4, rows));
         }
         spann_probe_rows_kernel<<<dim3((unsigned)((b * prow + 255) / 256)), 256, 0, ctx->stream>>>(rows, probes, pcnt, dfound, (uint32_t)ne, b, 0);
@@ -174,7 +164,8 @@ static mdb_status spann_search_impl(SpannSet& s, const float* queries, size_t b,
     }
     if (pio && pio->out) {
         // ---- the probes are the result
-        uint32_t* rows = mem == MDB_MEM_DEVICE ? pio->rows : (uint32_t*)(base + o_rows);
+        uint32_t* rows = pio->rows;
+        if (mem != MDB_MEM_DEVICE) MDB_TRY(mdb_scratch(ctx, b * prow * 4, (void**)&rows));
         spann_probe_rows_kernel<<<dim3((unsigned)((b * prow + 255) / 256)), 256, 0, ctx->stream>>>(rows, probes, pcnt, dfound, (uint32_t)ne, b, 1);
         MDB_HIP(ctx, hipGetLastError());
         if (mem == MDB_MEM_DEVICE) return MDB_OK;
@@ -191,9 +182,7 @@ static mdb_status spann_search_impl(SpannSet& s, const float* queries, size_t b,
     MDB_TRY(s.ivf.scan(dq, qstride, b, d_q_user, probes, pcnt, (int)ne, k, keys, cnts, &filt, srm.doc_out ? &srm : nullptr));
     if (block_out) {
         if (mem == MDB_MEM_DEVICE) return s.ivf.pack_points(keys, cnts, dfound, b, k, block_out);
-        MDB_TRY(s.ivf.pack_points(keys, cnts, dfound, b, k, base + o_blk));
-        const HostCopy back[1] = {{block_out, base + o_blk, mdb_points_block_bytes_impl(b, k)}};
-        return mdb_return_to_host(ctx, back, 1);
+        return s.ivf.pack_points_to_host(keys, cnts, dfound, b, k, block_out);
     }
     if (mem == MDB_MEM_DEVICE) {
         if (srm.done) {
@@ -205,8 +194,10 @@ static mdb_status spann_search_impl(SpannSet& s, const float* queries, size_t b,
         if (found_out) MDB_HIP(ctx, hipMemcpyAsync(found_out, dfound, b, hipMemcpyDeviceToDevice, ctx->stream));
         return MDB_OK;  // asynchronous on the context's stream, like every MDB_MEM_DEVICE call
     }
-    mdb_u128* ddoc = (mdb_u128*)(base + o_doc);
-    float* dsc = (float*)(base + o_sc);
+    mdb_u128* ddoc;
+    float* dsc;
+    MDB_TRY(mdb_scratch(ctx, b * ke * 16, (void**)&ddoc));
+    MDB_TRY(mdb_scratch(ctx, b * ke * 4, (void**)&dsc));
     MDB_TRY(s.ivf.remap(keys, cnts, b, k, d_q_user, ddoc, dsc, nullptr));
     const HostCopy back[4] = {{doc_ids_out, ddoc, total * 16}, {scores_out, dsc, total * 4}, {counts_out, cnts, b * 4}, {found_out, dfound, b}};
     return mdb_return_to_host(ctx, back, 4);
@@ -331,8 +322,7 @@ static mdb_status merge_shards_launch(mdb_ctx* ctx, const char* docs, size_t ds,
 mdb_status mdb_merge_shards(mdb_ctx* ctx, const mdb_u128* doc_ids, const float* scores, const uint32_t* counts, size_t world,
                             size_t b, size_t k, mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out) {
     if (!ctx || !doc_ids || !scores || !counts || !doc_ids_out || !scores_out || world == 0) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     return merge_shards_launch(ctx, (const char*)doc_ids, b * k * 16, (const char*)scores, b * k * 4, (const char*)counts, b * 4, world, b, k,
                                doc_ids_out, scores_out, counts_out);
 }
@@ -351,8 +341,7 @@ mdb_status mdb_shard_block_views(void* block, size_t b, size_t k, mdb_u128** doc
 mdb_status mdb_merge_shards_packed(mdb_ctx* ctx, const void* blocks, size_t world, size_t b, size_t k, mdb_u128* doc_ids_out,
                                    float* scores_out, uint32_t* counts_out) {
     if (!ctx || !blocks || !doc_ids_out || !scores_out || world == 0) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     const size_t stride = mdb_shard_block_bytes(b, k);
     const char* p = (const char*)blocks;
     return merge_shards_launch(ctx, p, stride, p + b * k * 16, stride, p + b * k * 20, stride, world, b, k, doc_ids_out, scores_out,
@@ -378,8 +367,7 @@ mdb_status mdb_allgather_merge(mdb_ctx* ctx, void* rccl_comm, const void* send_b
                                size_t k, mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out) {
     if (!ctx || !rccl_comm || !send_block || !recv_blocks || !doc_ids_out || !scores_out || world == 0) return MDB_ERR_INVALID_ARG;
     {
-        std::lock_guard<std::mutex> g(ctx->mu);
-        MDB_HIP(ctx, hipSetDevice(ctx->device));
+        MDB_ENTER(ctx);
         nccl_all_gather_fn ag = rccl_all_gather();
         if (!ag) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "librccl.so not found (dlopen): %s", dlerror());
         const int rc = ag(send_block, recv_blocks, mdb_shard_block_bytes(b, k), /*ncclUint8*/ 1, rccl_comm, ctx->stream);
@@ -391,8 +379,7 @@ mdb_status mdb_allgather_merge(mdb_ctx* ctx, void* rccl_comm, const void* send_b
 // the collective alone (hosts without torch): ncclAllGather(send -> recv, bytes_per_rank per rank) on the context's stream
 mdb_status mdb_allgather_blocks(mdb_ctx* ctx, void* rccl_comm, const void* send_block, void* recv_blocks, size_t bytes_per_rank) {
     if (!ctx || !rccl_comm || !send_block || !recv_blocks) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     nccl_all_gather_fn ag = rccl_all_gather();
     if (!ag) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "librccl.so not found (dlopen): %s", dlerror());
     const int rc = ag(send_block, recv_blocks, bytes_per_rank, /*ncclUint8*/ 1, rccl_comm, ctx->stream);
@@ -409,7 +396,7 @@ static mdb_status spann_merge_impl(SpannSet& s, const uint32_t* h_q_user, const 
     uint32_t* d_q_user = nullptr;
     if (h_q_user) {
         void* dev;
-        MDB_TRY(mdb_scratch(ctx, 14, b * 4, &dev));
+        MDB_TRY(mdb_scratch(ctx, b * 4, &dev));
         MDB_TRY(mdb_stage_small(ctx, h_q_user, b * 4, dev));
         d_q_user = (uint32_t*)dev;
     }
@@ -423,8 +410,7 @@ mdb_status mdb_spann_load(mdb_ctx* ctx, const void* hnsw_index, size_t hnsw_inde
                           size_t ivf_vectors_offset, const mdb_quant_desc* quant, mdb_spann** out) {
     if (!ctx || !hnsw_index || !hnsw_vectors || !ivf_index || !ivf_vectors || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     mdb_spann* sp = new mdb_spann();
     sp->set.ctx = ctx;
     sp->set.ivf.coarse_by_scan = false;
@@ -457,8 +443,7 @@ mdb_status mdb_spann_attach(mdb_ctx* ctx, mdb_spann* src, mdb_spann** out) { ret
 mdb_status mdb_spann_search(mdb_spann* sp, const float* queries, size_t b, const mdb_search_params* params, mdb_mem mem,
                             mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out, uint8_t* found_out) {
     if (!sp || (!queries && b) || !params || !doc_ids_out || !scores_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     return spann_search_impl(sp->set, queries, b, nullptr, params, mem, doc_ids_out, scores_out, counts_out, found_out);
 }
 
@@ -466,8 +451,7 @@ mdb_status mdb_spann_search_filtered(mdb_spann* sp, const float* queries, size_t
                                      const uint32_t* allow, size_t n_bitmaps, size_t words_per_bitmap, mdb_u128* doc_ids_out,
                                      float* scores_out, uint32_t* counts_out, uint8_t* found_out) {
     if (!sp || (!queries && b) || !params || !doc_ids_out || !scores_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     const SpannFilterArg fa{allow, n_bitmaps, words_per_bitmap};
     return spann_search_impl(sp->set, queries, b, nullptr, params, mem, doc_ids_out, scores_out, counts_out, found_out, &fa);
 }
@@ -476,8 +460,7 @@ mdb_status mdb_spann_search_submit(mdb_spann* sp, const float* queries, size_t b
                                    const uint32_t* allow, size_t n_bitmaps, size_t words_per_bitmap, mdb_u128* doc_ids_out,
                                    float* scores_out, uint32_t* counts_out, uint8_t* found_out) {
     if (!sp || (!queries && b) || !params || !doc_ids_out || !scores_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     const SpannFilterArg fa{allow, n_bitmaps, words_per_bitmap};
     return spann_search_impl(sp->set, queries, b, nullptr, params, MDB_MEM_HOST, doc_ids_out, scores_out, counts_out, found_out, &fa, true);
 }
@@ -485,8 +468,7 @@ mdb_status mdb_spann_search_submit(mdb_spann* sp, const float* queries, size_t b
 mdb_status mdb_spann_search_shard(mdb_spann* sp, const float* queries, size_t b, const mdb_search_params* params, mdb_mem mem,
                                   const uint32_t* allow, size_t n_bitmaps, size_t words_per_bitmap, void* block_out) {
     if (!sp || (!queries && b) || !params || !block_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     const SpannFilterArg fa{allow, n_bitmaps, words_per_bitmap};
     return spann_search_impl(sp->set, queries, b, nullptr, params, mem, nullptr, nullptr, nullptr, nullptr, &fa, false, block_out);
 }
@@ -494,23 +476,20 @@ mdb_status mdb_spann_search_shard(mdb_spann* sp, const float* queries, size_t b,
 mdb_status mdb_spann_merge_shards(mdb_spann* sp, const void* blocks, size_t world, size_t b, size_t k, mdb_u128* doc_ids_out,
                                   float* scores_out, uint32_t* counts_out, uint8_t* found_out) {
     if (!sp || !blocks || !doc_ids_out || !scores_out || world == 0) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     return spann_merge_impl(sp->set, nullptr, blocks, world, b, k, doc_ids_out, scores_out, counts_out, found_out);
 }
 
 
 mdb_status mdb_spann_invalidate(mdb_spann* sp, const mdb_u128* doc_ids, size_t n, uint8_t* flags_out) {
     if (!sp || (!doc_ids && n) || !flags_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     return sp->set.ivf.invalidate(0, doc_ids, n, flags_out, false);
 }
 
 mdb_status mdb_spann_is_invalidated(mdb_spann* sp, const mdb_u128* doc_ids, size_t n, uint8_t* flags_out) {
     if (!sp || (!doc_ids && n) || !flags_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(sp->set.ctx->mu);
-    MDB_HIP(sp->set.ctx, hipSetDevice(sp->set.ctx->device));
+    MDB_ENTER(sp->set.ctx);
     return sp->set.ivf.invalidate(0, doc_ids, n, flags_out, true);
 }
 
@@ -557,8 +536,7 @@ mdb_status mdb_multi_spann_load(mdb_ctx* ctx, const mdb_user_index_info* users, 
                                 const mdb_quant_desc* quant, uint32_t shard_rank, uint32_t shard_world, mdb_multi_spann** out) {
     if (!ctx || (!users && n_users) || !hnsw_index || !hnsw_vectors || !ivf_index || !ivf_vectors || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_ENTER(ctx);
     if (n_users == 0) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "no users");
     mdb_multi_spann* ms = new mdb_multi_spann();
     ms->set.ctx = ctx;
@@ -611,8 +589,7 @@ static mdb_status multi_spann_search_impl(mdb_multi_spann* ms, const mdb_u128* u
                                           uint32_t* counts_out, uint8_t* found_out, const SpannFilterArg* fa, bool submit,
                                           void* block_out = nullptr) {
     if (!ms || (!queries && b) || (!user_ids && b) || !params || (!block_out && (!doc_ids_out || !scores_out))) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     std::vector<uint32_t> qu(b);
     multi_spann_user_slots(ms, user_ids, b, qu.data());
     return spann_search_impl(ms->set, queries, b, qu.data(), params, mem, doc_ids_out, scores_out, counts_out, found_out, fa, submit, block_out);
@@ -657,8 +634,7 @@ size_t mdb_spann_probe_row_words(const mdb_search_params* params) {
 mdb_status mdb_multi_spann_probes(mdb_multi_spann* ms, const mdb_u128* user_ids, const float* queries, size_t b, const mdb_search_params* params,
                                   mdb_mem mem, uint32_t* rows_out) {
     if (!ms || (!queries && b) || (!user_ids && b) || !params || !rows_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     std::vector<uint32_t> qu(b);
     multi_spann_user_slots(ms, user_ids, b, qu.data());
     const SpannProbes pio{true, rows_out};
@@ -669,8 +645,7 @@ mdb_status mdb_multi_spann_search_shard_probes(mdb_multi_spann* ms, const mdb_u1
                                                const mdb_search_params* params, mdb_mem mem, const uint32_t* rows, const uint32_t* allow,
                                                size_t n_bitmaps, size_t words_per_bitmap, void* block_out) {
     if (!ms || (!queries && b) || (!user_ids && b) || !params || !rows || !block_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     std::vector<uint32_t> qu(b);
     multi_spann_user_slots(ms, user_ids, b, qu.data());
     const SpannFilterArg fa{allow, n_bitmaps, words_per_bitmap};
@@ -681,8 +656,7 @@ mdb_status mdb_multi_spann_search_shard_probes(mdb_multi_spann* ms, const mdb_u1
 mdb_status mdb_multi_spann_merge_shards(mdb_multi_spann* ms, const mdb_u128* user_ids, const void* blocks, size_t world, size_t b,
                                         size_t k, mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out, uint8_t* found_out) {
     if (!ms || (!user_ids && b) || !blocks || !doc_ids_out || !scores_out || world == 0) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     std::vector<uint32_t> qu(b);
     multi_spann_user_slots(ms, user_ids, b, qu.data());
     return spann_merge_impl(ms->set, qu.data(), blocks, world, b, k, doc_ids_out, scores_out, counts_out, found_out);
@@ -692,8 +666,7 @@ mdb_status mdb_multi_spann_merge_shards(mdb_multi_spann* ms, const mdb_u128* use
 mdb_status mdb_multi_spann_invalidate(mdb_multi_spann* ms, const mdb_u128* user_id, const mdb_u128* doc_ids, size_t n,
                                       uint8_t* flags_out) {
     if (!ms || !user_id || (!doc_ids && n) || !flags_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     auto it = ms->set.user_index.find(U128Key{user_id->lo, user_id->hi});
     if (it == ms->set.user_index.end()) {
         for (size_t i = 0; i < n; ++i) flags_out[i] = 0;
@@ -705,8 +678,7 @@ mdb_status mdb_multi_spann_invalidate(mdb_multi_spann* ms, const mdb_u128* user_
 mdb_status mdb_multi_spann_is_invalidated(mdb_multi_spann* ms, const mdb_u128* user_id, const mdb_u128* doc_ids, size_t n,
                                           uint8_t* flags_out) {
     if (!ms || !user_id || (!doc_ids && n) || !flags_out) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     auto it = ms->set.user_index.find(U128Key{user_id->lo, user_id->hi});
     if (it == ms->set.user_index.end()) return mdb_fail(ms->set.ctx, MDB_ERR_INVALID_ARG, "User not found");
     return ms->set.ivf.invalidate(it->second, doc_ids, n, flags_out, true);
@@ -718,8 +690,7 @@ mdb_status mdb_multi_spann_is_invalidated(mdb_multi_spann* ms, const mdb_u128* u
 // under by-user sharding, users of a table the log outlived) stay pending for ever in the reference too.
 mdb_status mdb_multi_spann_replay_invalidations(mdb_multi_spann* ms, const void* records, size_t n_records, size_t* n_applied_out) {
     if (!ms || (!records && n_records)) return MDB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(ms->set.ctx->mu);
-    MDB_HIP(ms->set.ctx, hipSetDevice(ms->set.ctx->device));
+    MDB_ENTER(ms->set.ctx);
     const uint8_t* rec = (const uint8_t*)records;
     std::unordered_map<uint32_t, std::vector<mdb_u128>> per_user;     // user slot -> its doc ids in log order
     for (size_t i = 0; i < n_records; ++i) {
