@@ -8,7 +8,7 @@
 // scan of `points`, graph_storage.rs:423-521).  Vectors are copied into 16-byte aligned rows.
 //
 // Search (BlockBasedHnsw::ann_search / search_layer, hnsw/block_based/index.rs:159-287): one
-// 256-thread block per query.  The traversal is inherently sequential in pops, so the block
+// 256-thread block per query (512 for the layer-0 instance of hnsw_beam_kernel: beam_block).  The traversal is inherently sequential in pops, so the block
 // parallelises INSIDE a step and keeps all state on chip:
 //   * candidates + working set: unsorted key arrays in LDS, wave 0 finds min / max with a
 //     wave-wide scan + DPP/shuffle reduce (replaces the two BinaryHeaps; same pop order: min
@@ -258,7 +258,7 @@ __device__ __forceinline__ const uint32_t* hnsw_upper_row(const HnswArgs& a, con
 // hnsw_search_kernel — the general traversal kernel (any ef <= 2*MDB_MAX_K): the working set W and the
 // candidates C are SORTED arrays in LDS (insert = ballot-counted shift).  The bench configuration
 // (ef <= 256) runs hnsw_beam_kernel below instead.
-template <int METRIC, bool VIS_LDS, int N16T>
+template <int METRIC, bool VIS_LDS, int N16T, int BLOCK = HNSW_BLOCK>
 __device__ void hnsw_general_traverse(const HnswArgs& a, const int qi, char* lds, const bool rezero_global_visited) {
     uint64_t* W = (uint64_t*)lds;
     uint64_t* C = W + a.ef_cap;
@@ -273,13 +273,13 @@ __device__ void hnsw_general_traverse(const HnswArgs& a, const int qi, char* lds
     const int grp = tid >> 4, j = tid & 15;
     const HnswUserDev u = a.users[a.q_user ? a.q_user[qi] : 0];
     if (!u.valid || u.n == 0 || u.num_layers == 0 || u.entry_point >= u.n) {
-        for (int i = tid; i < a.k; i += HNSW_BLOCK) a.out_keys[(size_t)qi * a.k + i] = MDB_KEY_MAX;
+        for (int i = tid; i < a.k; i += BLOCK) a.out_keys[(size_t)qi * a.k + i] = MDB_KEY_MAX;
         if (tid == 0) a.out_counts[qi] = 0;
         return;
     }
-    for (int i = tid; i < a.dpad; i += HNSW_BLOCK) qs[i] = a.q[(size_t)qi * a.qstride + i];
+    for (int i = tid; i < a.dpad; i += BLOCK) qs[i] = a.q[(size_t)qi * a.qstride + i];
     if (VIS_LDS || rezero_global_visited)
-        for (unsigned long long i = tid; i < a.vis_words; i += HNSW_BLOCK) vis[i] = 0;
+        for (unsigned long long i = tid; i < a.vis_words; i += BLOCK) vis[i] = 0;
     __syncthreads();
 
     const float* vecs = a.vecs + u.vec_off;
@@ -366,7 +366,7 @@ __device__ void hnsw_general_traverse(const HnswArgs& a, const int qi, char* lds
             const uint32_t nnew = misc[0];
             if (nnew == 0xFFFFFFFFu) break;
             // ---- P3 (all): exact distances, one 16-lane group per neighbour
-            for (uint32_t i = grp; i < nnew; i += HNSW_BLOCK / 16) {
+            for (uint32_t i = grp; i < nnew; i += BLOCK / 16) {
                 float d = MDB_GROUP_DIST(vecs + (size_t)nb_id[i] * a.dpad);
                 if (j == 0) nb_dist[i] = d;
             }
@@ -437,7 +437,7 @@ __device__ void hnsw_general_traverse(const HnswArgs& a, const int qi, char* lds
     // ---- result: W is sorted by (distance, id); truncate to k
     const int ws = (int)misc[2];
     const int outc = ws < a.k ? ws : a.k;
-    for (int i = tid; i < a.k; i += HNSW_BLOCK) a.out_keys[(size_t)qi * a.k + i] = i < outc ? W[i] : MDB_KEY_MAX;
+    for (int i = tid; i < a.k; i += BLOCK) a.out_keys[(size_t)qi * a.k + i] = i < outc ? W[i] : MDB_KEY_MAX;
     if (tid == 0) {
         a.out_counts[qi] = (uint32_t)outc;
         atomicAdd(&a.counters[0], evals);
@@ -731,11 +731,26 @@ __global__ __launch_bounds__(BLOCK) void hnsw_closure_kernel(HnswArgs a, int wca
 #ifndef MDB_HNSW_L0TOUCH
 #define MDB_HNSW_L0TOUCH 1
 #endif
+// threads of a block: wave 0 runs the traversal, the others are distance groups of 16 lanes.  The layer-0 instance has seven
+// distance waves (28 groups): by a CPU estimate on a 100 k k-NN graph 99.8 % of its steps bring at most 28 new neighbours (23 % bring
+// more than the 12 that three waves hold) and then take the one-vector-per-group path whose gather is requested right behind the barrier, in a single pass.  The CU holds
+// one block either way (LDS), so the extra waves take slots nobody uses.
+#ifndef MDB_HNSW_L0_BLOCK
+#define MDB_HNSW_L0_BLOCK 512
+#endif
+// MDB_HNSW_L0_IDLE4: wave 4 — the one that shares wave 0's SIMD — only attends the barriers (six distance waves, 24 groups)
+#ifndef MDB_HNSW_L0_IDLE4
+#define MDB_HNSW_L0_IDLE4 0
+#endif
+__host__ __device__ constexpr int beam_block(bool l0) { return l0 ? MDB_HNSW_L0_BLOCK : HNSW_BLOCK; }
 // W (the sorted working set of the result: 64 NB keys rounded to 2 / 4 KB) | C 1024 keys | nb_id | nb_dist | misc | qs | vis
 __host__ __device__ constexpr int beam_lds_c(int nb) { return nb <= 5 ? 2048 : 4096; }
 __host__ __device__ constexpr int beam_lds_qs(int nb) { return beam_lds_c(nb) + 8192 + 1024 + 1024 + 64; }
 
-#ifdef MDB_PIPE_DBG   // cycle / event accounting of the roles into counters[4..15] (MDB_HNSW_DBG=1 prints them)
+#ifdef MDB_PIPE_DBG   // cycle / event accounting of the roles into counters[4..15] (MDB_HNSW_DBG=1 prints them): cycles of P2 | barrier |
+// shadow (selection) | barrier | P4, steps, steps with > 12 / > 24 / > 28 new neighbours, a distance wave's phase, compactions by bound / by select.
+// hnsw_upper_kernel (mdb_hnsw_upper.hip) adds ITS phases and counts into the same words (slots 6-8 there: new neighbours, survivors,
+// accepted; 10 / 11: compactions by bound / by select, as here): build one of the two files with the flag at a time
 #define PIPE_TB(t) const unsigned long long t = __builtin_readcyclecounter()
 #define PIPE_TE(slot, t) dbg_acc[slot] += __builtin_readcyclecounter() - (t)
 #define PIPE_CNT(slot, v) dbg_acc[slot] += (v)
@@ -753,10 +768,13 @@ __host__ __device__ constexpr int beam_lds_qs(int nb) { return beam_lds_c(nb) + 
 // NB: registers of 64 beam slots — 5 (320 slots) serves ef <= 256, 8 (512 slots; layer-0 instance only) ef <= 448: both leave >= 64 slots
 // for ties with furthest before the general traversal has to take the query over.
 template <int METRIC, bool VIS_LDS, int N16T, bool ROW64, bool L0 = false, int NB = 5>
-__global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
+__global__ __launch_bounds__(beam_block(L0)) void hnsw_beam_kernel(HnswArgs a) {
     constexpr int NCH = ROW64 ? 1 : 4;   // 64-edge chunks of a row
     constexpr bool SPEC = MDB_HNSW_SPEC && N16T > 0 && N16T <= 16;   // the groups' first vector is requested ahead of the list length
-    constexpr int BLK = HNSW_BLOCK;
+    constexpr int BLK = beam_block(L0);
+    static_assert(BLK % 64 == 0 && BLK >= 128 && BLK <= 1024, "a block is wave 0 and one to fifteen distance waves");
+    constexpr bool IDLE4 = MDB_HNSW_L0_IDLE4 && BLK == 512;
+    constexpr int NG = (BLK - 64 - (IDLE4 ? 64 : 0)) / 16;   // distance groups
     extern __shared__ __attribute__((aligned(16))) char lds[];
     // FIXED LDS layout (compile-time offsets: the kernel is SGPR-bound, eight live LDS pointers are eight
     // scalars it does not have): W 256 keys | C 1024 keys | nb_id 256 | nb_dist 256 | misc 16 | qs dpad | vis
@@ -775,6 +793,8 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform
     const int grp = tid >> 4, j = tid & 15;
+    const bool dwave = wave != 0 && !(IDLE4 && wave == 4);          // a distance wave
+    const int gi = grp - 4 - (IDLE4 && wave > 4 ? 4 : 0);           // its groups' numbers: 0 .. NG-1
     const HnswUserDev u = a.users[a.q_user ? a.q_user[qi] : 0];
     if (!u.valid || u.n == 0 || u.num_layers == 0 || u.entry_point >= u.n) {
         for (int i = tid; i < a.k; i += BLK) a.out_keys[(size_t)qi * a.k + i] = MDB_KEY_MAX;
@@ -784,7 +804,7 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
     for (int i = tid; i < a.dpad; i += BLK) qs[i] = a.q[(size_t)qi * a.qstride + i];
     if (VIS_LDS)
         for (unsigned long long i = tid; i < a.vis_words; i += BLK) vis[i] = 0;
-    if (tid < 16) nb_id[tid] = 0;   // the groups' speculative first fetch reads its slot before any list was written: row 0 exists
+    if (tid < NG) nb_id[tid] = 0;   // the groups' speculative first fetch reads its slot before any list was written: row 0 exists
     __syncthreads();
     if (L0) {
         // the visited set is shared by the layers (one SearchContext per ann_search, index.rs:172)
@@ -956,14 +976,14 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
             // right behind the barrier, in parallel with the read of misc[0] (slots past the list hold ids of earlier steps — valid
             // rows, their values unused); the length used to sit in front of both round trips
             float4 sx[SPEC ? N16T / 4 : 1];
-            if (SPEC && wave != 0) {
-                const float4* x4 = (const float4*)(vecs + (size_t)nb_id[grp - 4] * a.dpad + j * N16T);
+            if (SPEC && dwave) {
+                const float4* x4 = (const float4*)(vecs + (size_t)nb_id[gi] * a.dpad + j * N16T);
 #pragma unroll
                 for (int c = 0; c < (SPEC ? N16T / 4 : 1); ++c) sx[c] = x4[c];
             }
             const uint32_t nnew = misc[0];
             if (nnew == 0xFFFFFFFFu) break;
-            if (wave == 0) PIPE_CNT(5, 1);
+            if (wave == 0) { PIPE_CNT(5, 1); PIPE_CNT(6, nnew > 12u ? 1 : 0); PIPE_CNT(7, nnew > 24u ? 1 : 0); PIPE_CNT(8, nnew > 28u ? 1 : 0); }
             if (wave == 0) {
                 // ---- in the shadow of P3: the best candidate already in B (the next pop unless a neighbour
                 // accepted below beats it) and, speculatively, its adjacency row
@@ -994,14 +1014,13 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
                         }
                     }
                 }
-            } else {
-                // ---- P3 (waves 1-3): exact distances, one 16-lane group per neighbour
+            } else if (dwave) {
+                // ---- P3 (the distance waves): exact distances, one 16-lane group per neighbour
                 // (the groups also take the order-preserving integer image and the NaN check off wave 0's path)
-                constexpr int NG = (HNSW_BLOCK - 64) / 16;
                 if (N16T > 0 && N16T <= 16 && nnew > (uint32_t)NG) {
                     // more neighbours than groups (the fill phase of a layer): every group takes two, so that up to
                     // 2 NG evaluations share one gather latency
-                    for (uint32_t i = grp - 4; i < nnew; i += 2 * NG) {
+                    for (uint32_t i = gi; i < nnew; i += 2 * NG) {
                         const bool two = i + NG < nnew;
                         const uint32_t i2 = two ? i + NG : i;
                         float da, db;
@@ -1015,7 +1034,7 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
                         }
                     }
                 } else if (SPEC) {
-                    const uint32_t i = grp - 4;   // nnew <= NG: one neighbour per group at most, already on its way
+                    const uint32_t i = gi;   // nnew <= NG: one neighbour per group at most, already on its way
                     if (i < nnew) {
                         float acc = 0.0f;
 #pragma unroll
@@ -1032,7 +1051,7 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
                         }
                     }
                 } else {
-                    for (uint32_t i = grp - 4; i < nnew; i += NG) {
+                    for (uint32_t i = gi; i < nnew; i += NG) {
                         float d = MDB_BEAM_DIST(vecs + (size_t)nb_id[i] * a.dpad);
                         if (j == 0) {
                             nb_od[i] = f32_orderable(d);
@@ -1041,13 +1060,13 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
                     }
                 }
             }
-            if (L0TOUCH && wave != 0) {
+            if (L0TOUCH && dwave) {
                 // ---- layer 0: every point that is evaluated may be popped later, and its adjacency row (256 MB of rows at 1 M points)
                 // then comes from HBM, ~1.1 k cycles, in front of wave 0's touches.  The group that evaluates a point touches the
                 // point's row lines as well: when the point becomes the runner-up, its row is in L2 or the Infinity Cache.
                 asm volatile("" ::"v"(row_hold));   // last step's touch ends here (the distances above are done: the groups only wait for wave 0 now)
                 const uint32_t lines = (stride + 31) / 32;
-                for (uint32_t i = grp - 4; i < nnew; i += (HNSW_BLOCK - 64) / 16)
+                for (uint32_t i = gi; i < nnew; i += NG)
                     if ((uint32_t)j < lines) row_hold = adj_base[(size_t)nb_id[i] * stride + 32 * j];
             }
             if (wave == 0) PIPE_TE(2, t_sh);
@@ -1083,42 +1102,10 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
                     const int na = __popcll(accepted);
                     if (na) {
                         if (n + na > (64 * NB)) {
-                            // ---- compaction: f = ef-th smallest distance image in B (32-step radix select by
-                            // ballots; EMPTY = 0xFFFFFFFF sorts last), drop everything farther than f
-                            uint32_t prefix = 0;
-                            int need = ef;
-                            for (int bit = 31; bit >= 0; --bit) {
-                                const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
-                                int cnt0 = 0;
-#pragma unroll
-                                for (int r = 0; r < NB; ++r)
-                                    cnt0 += __popcll(__ballot((((bd[r] ^ prefix) & hi_mask) == 0u) && !((bd[r] >> bit) & 1u)));
-                                if (cnt0 < need) { need -= cnt0; prefix |= 1u << bit; }
-                            }
-                            const uint32_t f = prefix;
-                            int kept = 0;
-#pragma unroll
-                            for (int r = 0; r < NB; ++r) {
-                                const bool keep = bd[r] <= f;  // EMPTY never kept (f is a real distance: n > ef here)
-                                const unsigned long long km = __ballot(keep);
-                                if (keep) {
-                                    const int pos = kept + __popcll(km & lt_mask);
-                                    C[pos] = ((uint64_t)bd[r] << 32) | bi[r];
-                                    stage_flag[pos] = cdv[r] != SLOT_EMPTY ? 1u : 0u;
-                                }
-                                kept += __popcll(km);
-                            }
-#pragma unroll
-                            for (int r = 0; r < NB; ++r) {
-                                const int idx = lane + 64 * r;
-                                const bool in = idx < kept;
-                                const uint64_t kk = in ? C[idx] : 0;
-                                bd[r] = in ? (uint32_t)(kk >> 32) : SLOT_EMPTY;
-                                bi[r] = in ? (uint32_t)kk : 0u;
-                                cdv[r] = (in && stage_flag[idx] != 0u) ? bd[r] : SLOT_EMPTY;
-                            }
-                            n = kept;
-                            fbound = min(fbound, f);
+                            // ---- compaction (beam_compact): whatever lies beyond the bound `fbound` when that frees enough slots, else beyond
+                            // the exact ef-th smallest distance image of B
+                            const bool by_bound = beam_compact<NB>(bd, bi, cdv, n, fbound, ef, na, C, stage_flag, lane, lt_mask);
+                            PIPE_CNT(by_bound ? 10 : 11, 1);
                             if (n + na > (64 * NB)) { overflow = true; break; }  // > ~120 exact ties with furthest
                             if (best_have) {  // the best accepted so far may have been dropped (rare)
                                 bool still = false;
@@ -1305,7 +1292,7 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
     uint64_t* const okeys = ap->out_keys;
     for (int i = tid; i < kk; i += BLK) okeys[(size_t)qi * kk + i] = i < outc ? W[i] : MDB_KEY_MAX;
 #ifdef MDB_PIPE_DBG
-    if (lane == 0 && (wave == 0 || wave == 1 || wave == 5))
+    if (lane == 0 && wave <= 1)   // (wave 0: the traversal's phases and counts; wave 1: slot 9, a distance wave's phase)
         for (int i = 0; i < 12; ++i)
             if (dbg_acc[i]) atomicAdd(&ap->counters[4 + i], dbg_acc[i]);
 #endif
@@ -1323,7 +1310,7 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_beam_kernel(HnswArgs a) {
     // the general algorithm (sorted LDS sets, room for ~800 ties); rows and counters come from that run
     if (misc[3]) {
         const HnswArgs a2 = *ap;
-        hnsw_general_traverse<METRIC, VIS_LDS, N16T>(a2, qi, lds, true);
+        hnsw_general_traverse<METRIC, VIS_LDS, N16T, BLK>(a2, qi, lds, true);
     }
     if (L0 && ap->rm_doc) {
         __syncthreads();   // the keys (this block's own stores, whichever traversal wrote them) are visible to the whole block
@@ -1864,7 +1851,7 @@ mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32
                 const dim3 grid((unsigned)b);
                 if (table)   // layer 0 behind the table pass: the beam's registers as in upper_launch_bottom
                     return mdb_pick<4, 5, 8>(hnsw_beam_nb4(ctx, ef) ? 4 : ef <= 256 ? 5 : 8, [&](auto NB) {
-                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), true, true, NB()>, grid, HNSW_BLOCK, lds, a);
+                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), true, true, NB()>, grid, beam_block(true), lds, a);
                     });
                 if (beam)
                     return mdb_pick_bool(row64, [&](auto R64) {

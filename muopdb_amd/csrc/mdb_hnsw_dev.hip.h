@@ -67,3 +67,70 @@ __device__ __forceinline__ bool beam_best_id(const uint32_t (&cdv)[NB], const ui
     return true;
 }
 
+// Compaction of the over-full beam B (`n + na > 64 NB`: the step's `na` accepted neighbours find no free slots).  Everything
+// farther than furthest.distance may go: it is outside the working set W and cannot tie with furthest; what is kept goes through
+// the staging words (C / stage_flag: 64 NB keys / flags of LDS) into slots 0 .. kept-1, in slot order.
+//  * bound first: `fbound` — the accept test's prefilter, refreshed whenever a prefilter survivor is rejected — is an upper bound
+//    of furthest.distance as it will be once this step's accepted neighbours are in.  When the slots within fbound leave room
+//    (16 free slots behind the `na` pushes, so that the next compaction is not the next step's), exactly those
+//    are kept: NB ballots.  B then holds W and a few slots between furthest and fbound — the same kind of slot it holds between
+//    two compactions anyway (the counts of the accept and stop tests never see a slot beyond furthest);
+//  * otherwise (no rejection yet on this layer: fbound == SLOT_EMPTY; or a long run of ties at the bound) the exact ef-th smallest
+//    image of B by a 32-step ballot radix select (EMPTY = 0xFFFFFFFF sorts last) — 32 NB ballots on a lone wave.
+// n and fbound are updated; returns true when the bound sufficed.  The caller re-checks `n + na` (overflow) and re-selects its
+// runner-up, which may have been dropped.
+#ifndef MDB_HNSW_BOUND_COMPACT
+#define MDB_HNSW_BOUND_COMPACT 1
+#endif
+template <int NB>
+__device__ __forceinline__ bool beam_compact(uint32_t (&bd)[NB], uint32_t (&bi)[NB], uint32_t (&cdv)[NB], int& n, uint32_t& fbound,
+                                             const int ef, const int na, uint64_t* const C, uint32_t* const stage_flag, const int lane,
+                                             const unsigned long long lt_mask) {
+    constexpr int MARGIN = 16;   // free slots the bound drop must leave behind the pushes
+    bool by_bound = false;
+    if (MDB_HNSW_BOUND_COMPACT && fbound != SLOT_EMPTY) {
+        int c = 0;
+#pragma unroll
+        for (int r = 0; r < NB; ++r) c += __popcll(__ballot(bd[r] <= fbound));
+        by_bound = c + na <= 64 * NB - MARGIN;
+    }
+    uint32_t f = fbound;
+    if (!by_bound) {
+        uint32_t prefix = 0;
+        int need = ef;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
+            int cnt0 = 0;
+#pragma unroll
+            for (int r = 0; r < NB; ++r)
+                cnt0 += __popcll(__ballot((((bd[r] ^ prefix) & hi_mask) == 0u) && !((bd[r] >> bit) & 1u)));
+            if (cnt0 < need) { need -= cnt0; prefix |= 1u << bit; }
+        }
+        f = prefix;
+    }
+    int kept = 0;
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+        const bool keep = bd[r] <= f;  // EMPTY never kept (f is a real distance: n > ef here)
+        const unsigned long long km = __ballot(keep);
+        if (keep) {
+            const int pos = kept + __popcll(km & lt_mask);
+            C[pos] = ((uint64_t)bd[r] << 32) | bi[r];
+            stage_flag[pos] = cdv[r] != SLOT_EMPTY ? 1u : 0u;
+        }
+        kept += __popcll(km);
+    }
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+        const int idx = lane + 64 * r;
+        const bool in = idx < kept;
+        const uint64_t kk = in ? C[idx] : 0;
+        bd[r] = in ? (uint32_t)(kk >> 32) : SLOT_EMPTY;
+        bi[r] = in ? (uint32_t)kk : 0u;
+        cdv[r] = (in && stage_flag[idx] != 0u) ? bd[r] : SLOT_EMPTY;
+    }
+    n = kept;
+    fbound = min(fbound, f);
+    return by_bound;
+}
+

@@ -484,48 +484,16 @@ __device__ __forceinline__ void upper_traverse_wave0(const HnswUpArgs& a, const 
                 }
                 const int na = __popcll(accepted);
                 UP_T(t3);
-                UP_ACC(2, t3 - t2); UP_CNT(8, na); UP_CNT(9, na == 1 ? 1 : 0); UP_CNT(10, na >= 3 ? 1 : 0);
+                UP_ACC(2, t3 - t2); UP_CNT(8, na); UP_CNT(9, na == 1 ? 1 : 0);
                 if (na) {
                     if (n + na > (64 * NB)) {
-                        UP_CNT(11, 1);
-                        // ---- compaction: f = ef-th smallest distance image in B (32-step radix select by ballots), drop what is farther
-                        uint32_t prefix = 0;
-                        int need = ef;
-                        for (int b = 31; b >= 0; --b) {
-                            const uint32_t hi_mask = b == 31 ? 0u : (0xFFFFFFFFu << (b + 1));
-                            int cnt0 = 0;
-#pragma unroll
-                            for (int r = 0; r < NB; ++r)
-                                cnt0 += __popcll(__ballot((((bd[r] ^ prefix) & hi_mask) == 0u) && !((bd[r] >> b) & 1u)));
-                            if (cnt0 < need) { need -= cnt0; prefix |= 1u << b; }
-                        }
-                        const uint32_t f = prefix;
-                        int kept = 0;
-#pragma unroll
-                        for (int r = 0; r < NB; ++r) {
-                            const bool keep = bd[r] <= f;
-                            const unsigned long long km = __ballot(keep);
-                            if (keep) {
-                                const int pos = kept + __popcll(km & lt_mask);
-                                C[pos] = ((uint64_t)bd[r] << 32) | bi[r];
-                                stage_flag[pos] = cdv[r] != SLOT_EMPTY ? 1u : 0u;
-                            }
-                            kept += __popcll(km);
-                        }
-#pragma unroll
-                        for (int r = 0; r < NB; ++r) {
-                            const int idx = lane + 64 * r;
-                            const bool in = idx < kept;
-                            const uint64_t kk = in ? C[idx] : 0;
-                            bd[r] = in ? (uint32_t)(kk >> 32) : SLOT_EMPTY;
-                            bi[r] = in ? (uint32_t)kk : 0u;
-                            cdv[r] = (in && stage_flag[idx] != 0u) ? bd[r] : SLOT_EMPTY;
-                        }
-                        n = kept;
+                        // ---- compaction (beam_compact): whatever lies beyond the bound `fbound` when that frees enough slots, else beyond
+                        // the exact ef-th smallest distance image of B
+                        const bool by_bound = beam_compact<NB>(bd, bi, cdv, n, fbound, ef, na, C, stage_flag, lane, lt_mask);
+                        UP_CNT(by_bound ? 10 : 11, 1);   // slot 10: by the bound, slot 11: by the exact select
                         nexp = 0;
 #pragma unroll
                         for (int r = 0; r < NB; ++r) nexp += __popcll(__ballot(bd[r] != SLOT_EMPTY && cdv[r] == SLOT_EMPTY));
-                        fbound = min(fbound, f);
                         if (n + na > (64 * NB)) { overflow = true; break; }
                         ru_valid = beam_best_id(cdv, bi, ru_o, ru_id);  // may have been dropped
                         if (ru_valid) rowr = load_row(ru_id);
