@@ -383,7 +383,7 @@ __device__ void hnsw_general_traverse(const HnswArgs& a, const int qi, char* lds
                     const bool have0 = i < nnew;
                     const float d = have0 ? nb_dist[i] : 0.0f;
                     const uint32_t id = have0 ? nb_id[i] : 0;
-                    if (have0 && d != d) nan_seen = true;
+                    if (__ballot(have0 && d != d)) nan_seen = true;   // (every lane learns it: lane 0 alone reports at the end)
                     const bool have = have0 && d == d;
                     const uint32_t od = f32_orderable(d);
                     const bool full = wsize >= ef;

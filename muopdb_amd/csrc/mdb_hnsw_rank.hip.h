@@ -312,7 +312,7 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
             uint32_t* nxt = fr + 64;
             if (lane == 0) { atomicOr(&vis[ep >> 5], 1u << (ep & 31)); cur[0] = ep; }
             uint32_t ncur = 1;
-            uint32_t best = 0xFFFFFFFFu;
+            uint32_t best = 0xFFFFFFFFu, worst = 0u;
             while (ncur > 0) {
                 uint32_t nnext = 0;
                 for (uint32_t base = 0; base < ncur; base += per) {
@@ -320,7 +320,11 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
                     const bool act = pi < ncur;
                     const uint32_t f = act ? cur[pi] : 0u;
                     const uint32_t nbr = (act && slot < su) ? lrows[(size_t)f * su + slot] : 0xFFFFFFFFu;
-                    if (act && slot == 0) best = min(best, (uint32_t)R[f] & 0x7FFFu);
+                    if (act && slot == 0) {
+                        const uint32_t rr = (uint32_t)R[f] & 0x7FFFu;
+                        best = min(best, rr);
+                        worst = max(worst, rr);   // (a NaN distance ranks LAST: the lowest rank met says nothing about it)
+                    }
                     expanded += (uint32_t)__popcll(__ballot(act && slot == 0 && nbr != 0xFFFFFFFFu));  // rows are packed
                     bool isnew = false;
                     if (nbr != 0xFFFFFFFFu) {
@@ -335,7 +339,7 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
                 ncur = nnext;
                 uint32_t* t = cur; cur = nxt; nxt = t;
             }
-            if (__ballot(best != 0xFFFFFFFFu && best >= nan_start)) nan_seen = true;
+            if (__ballot(best != 0xFFFFFFFFu && worst >= nan_start)) nan_seen = true;   // every point of the closure was evaluated
             const uint32_t rb = wave_min_u32(best);
             ep = rk_first((uint32_t)P[rb]) & 0x7FFFu;
             continue;
@@ -522,7 +526,7 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
             uint32_t* nxt = fr + 64;
             if (lane == 0) { atomicOr(&vis[ep >> 5], 1u << (ep & 31)); cur[0] = ep; }
             uint32_t ncur = 1;
-            uint32_t best = 0xFFFFFFFFu;
+            uint32_t best = 0xFFFFFFFFu, worst = 0u;
             while (ncur > 0) {
                 uint32_t nnext = 0;
                 for (uint32_t base = 0; base < ncur; base += per) {
@@ -530,7 +534,11 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
                     const bool act = pi < ncur;
                     const uint32_t f = act ? cur[pi] : 0u;
                     const uint32_t nbr = (act && slot < su) ? lrows[(size_t)f * su + slot] : 0xFFFFFFFFu;
-                    if (act && slot == 0) best = min(best, (uint32_t)R[f] & 0x7FFFu);
+                    if (act && slot == 0) {
+                        const uint32_t rr = (uint32_t)R[f] & 0x7FFFu;
+                        best = min(best, rr);
+                        worst = max(worst, rr);   // (a NaN distance ranks LAST: the lowest rank met says nothing about it)
+                    }
                     expanded += (uint32_t)__popcll(__ballot(act && slot == 0 && nbr != 0xFFFFFFFFu));  // rows are packed
                     bool isnew = false;
                     if (nbr != 0xFFFFFFFFu) {
@@ -545,7 +553,7 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
                 ncur = nnext;
                 uint32_t* t = cur; cur = nxt; nxt = t;
             }
-            nanm |= __ballot(best != 0xFFFFFFFFu && best >= nan_start);
+            nanm |= __ballot(best != 0xFFFFFFFFu && worst >= nan_start);   // every point of the closure was evaluated
             const uint32_t rb = wave_min_u32(best);
             ep = rk_first((uint32_t)P[rb]) & 0x7FFFu;
             continue;

@@ -462,6 +462,9 @@ struct IvfStorage {
 static const uint32_t* g_allow_base = nullptr;   // [b][g_allow_stride] words, set by orc_set_filter
 static size_t g_allow_stride = 0;
 static thread_local const uint32_t* tl_allow = nullptr;  // bitmap of the query being served by this thread
+// set where a NaN distance makes scan_posting_list give up: the reference PANICS there (PointAndDistance::new, utils.rs:79-80), which no
+// `.ok()` of a caller turns into None
+static thread_local bool tl_nan_panic = false;
 static inline void select_filter(size_t qi) { tl_allow = g_allow_base ? g_allow_base + qi * g_allow_stride : nullptr; }
 
 struct Ivf {
@@ -510,7 +513,7 @@ struct Ivf {
             if (invalid_point_ids.count(pid)) continue;
             if (pid >= vec.num_vectors) return false;  // "index out of bounds"
             float dist = quantizer_distance(qquery, vec.get(pid));
-            if (std::isnan(dist)) return false;
+            if (std::isnan(dist)) { tl_nan_panic = true; return false; }
             out.push_back({dist, pid});
         }
         std::stable_sort(out.begin(), out.end(),
@@ -761,7 +764,9 @@ struct Spann {
             float rhs = nearest * p.centroid_distance_ratio;
             if (lhs <= rhs) ids.push_back((size_t)c.doc_id);  // :239-246
         }
-        if (!posting_lists.search_with_centroids_and_remap(query, ids, p.top_k, out)) return 0;  // .ok()?
+        tl_nan_panic = false;
+        if (!posting_lists.search_with_centroids_and_remap(query, ids, p.top_k, out))
+            return tl_nan_panic ? -1 : 0;  // `.ok()?` :263 maps an Err to None; a NaN distance is a panic, not an Err
         return 1;
     }
 };
