@@ -103,6 +103,30 @@ typedef struct mdb_hnsw mdb_hnsw;
 typedef struct mdb_spann mdb_spann;
 typedef struct mdb_multi_spann mdb_multi_spann;
 
+/* ---------------------------------------------------------------- Limits
+ * What the on-chip selectors, traversal state and merges are sized for.  MDB_MAX_K = 2048 (csrc/mdb_common.h); the largest ef is
+ * 2 * MDB_MAX_K = 4096; HNSW_MAX_STRIDE = 256 (csrc/mdb_hnsw.hip).  Every excess below is refused on the host, before any launch,
+ * with the status given and a message in mdb_last_error; the handle and the context serve the next call as if nothing had
+ * happened (a refused *_submit leaves nothing pending, a refused MDB_MEM_DEVICE call defers nothing to mdb_sync).  The same
+ * table is in INTEGRATION.md; tests/test_gpu_limits.py runs every row at its limit and one past it.
+ *
+ * | entry point | limit | past it |
+ * | mdb_flat_search, mdb_flat_topk | k <= 2048 | MDB_ERR_UNSUPPORTED |
+ * | mdb_ivf_search, _search_filtered, _search_points, _search_submit, _search_shard | k <= 2048 | MDB_ERR_UNSUPPORTED |
+ * | mdb_ivf_search* with probes == NULL, mdb_ivf_find_nearest_centroids | num_probes <= min(2048, num_clusters) | MDB_ERR_UNSUPPORTED above 2048, MDB_ERR_OUT_OF_RANGE above num_clusters or at 0 |
+ * | mdb_ivf_search* with explicit probes | any number of probe columns | - |
+ * | mdb_ivf_coarse_keys | num_probes <= 2048 | MDB_ERR_OUT_OF_RANGE |
+ * | mdb_ivf_merge_coarse_keys | num_probes <= 2048 | MDB_ERR_UNSUPPORTED |
+ * | mdb_ivf_assign | max_clusters_per_vector <= min(2048, num_centroids) | MDB_ERR_UNSUPPORTED above 2048, MDB_ERR_OUT_OF_RANGE above num_centroids or at 0 |
+ * | mdb_hnsw_ann_search, _ann_search_submit | k <= 2048, ef <= 4096 | MDB_ERR_UNSUPPORTED |
+ * | mdb_hnsw_load, mdb_spann_load, mdb_multi_spann_load | node degree <= 256, num_layers <= 255 | MDB_ERR_UNSUPPORTED |
+ * | mdb_hnsw_select_neighbors | 1 <= max_neighbors <= 64 | MDB_ERR_UNSUPPORTED |
+ * | mdb_quant_desc (every *_load, mdb_pq_*) | 1 <= num_bits <= 8 | MDB_ERR_UNSUPPORTED |
+ * | mdb_spann_search*, mdb_multi_spann_search*, _search_shard*, mdb_multi_spann_probes | top_k <= 2048, num_explored_centroids <= 2048, ef_construction <= 4096 | MDB_ERR_UNSUPPORTED |
+ * | mdb_ivf_merge_shards, mdb_spann_merge_shards, mdb_multi_spann_merge_shards | k <= 2048 and world * k * 8 + k * 20 + (world + 1) * 4 + 16 <= 153600 (k <= 2048 up to world = 6, 2020 at world = 7, 1827 at world = 8) | MDB_ERR_UNSUPPORTED |
+ * | mdb_merge_shards, mdb_merge_shards_packed, mdb_allgather_merge (after its all-gather) | world * k * 20 + (world + 1) * 4 + 16 <= 153600 (k <= 3839 / 1919 / 959 at world = 2 / 4 / 8) | MDB_ERR_UNSUPPORTED |
+ */
+
 /* ---------------------------------------------------------------- context */
 mdb_status mdb_device_open(int gpu, mdb_ctx** out);
 /* drops the caller's reference; index handles created on the context keep it alive until they
