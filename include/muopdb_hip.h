@@ -108,7 +108,8 @@ typedef struct mdb_multi_spann mdb_multi_spann;
  * 2 * MDB_MAX_K = 4096; HNSW_MAX_STRIDE = 256 (csrc/mdb_hnsw.hip).  Every excess below is refused on the host, before any launch,
  * with the status given and a message in mdb_last_error; the handle and the context serve the next call as if nothing had
  * happened (a refused *_submit leaves nothing pending, a refused MDB_MEM_DEVICE call defers nothing to mdb_sync).  The same
- * table is in INTEGRATION.md; tests/test_gpu_limits.py runs every row at its limit and one past it.
+ * table is in INTEGRATION.md; tests/test_gpu_limits.py runs every row at its limit and one past it (the last row:
+ * tests/test_gpu_async_stream.py).
  *
  * | entry point | limit | past it |
  * | mdb_flat_search, mdb_flat_topk | k <= 2048 | MDB_ERR_UNSUPPORTED |
@@ -125,6 +126,7 @@ typedef struct mdb_multi_spann mdb_multi_spann;
  * | mdb_spann_search*, mdb_multi_spann_search*, _search_shard*, mdb_multi_spann_probes | top_k <= 2048, num_explored_centroids <= 2048, ef_construction <= 4096 | MDB_ERR_UNSUPPORTED |
  * | mdb_ivf_merge_shards, mdb_spann_merge_shards, mdb_multi_spann_merge_shards | k <= 2048 and world * k * 8 + k * 20 + (world + 1) * 4 + 16 <= 153600 (k <= 2048 up to world = 6, 2020 at world = 7, 1827 at world = 8) | MDB_ERR_UNSUPPORTED |
  * | mdb_merge_shards, mdb_merge_shards_packed, mdb_allgather_merge (after its all-gather) | world * k * 20 + (world + 1) * 4 + 16 <= 153600 (k <= 3839 / 1919 / 959 at world = 2 / 4 / 8) | MDB_ERR_UNSUPPORTED |
+ * | MDB_MEM_HOST calls and mdb_*_search_submit while a submitted call is pending on the context | one pending call per context | MDB_ERR_INVALID_ARG, the pending call is untouched; an MDB_MEM_DEVICE call IS accepted: mdb_wait reports the submitted call's status, mdb_sync the device call's, whichever is called first |
  */
 
 /* ---------------------------------------------------------------- context */
@@ -133,9 +135,33 @@ mdb_status mdb_device_open(int gpu, mdb_ctx** out);
  * are freed, so the order of mdb_*_free and mdb_device_close does not matter */
 void mdb_device_close(mdb_ctx* ctx);
 /* run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the legacy
- * default (null) stream.  A context starts on its own non-blocking stream. */
+ * default (null) stream.  The call first drains the stream the context was on (and destroys it if it was the context's own);
+ * the borrowed stream must outlive the context and every handle created on it.
+ *
+ * A context starts on its OWN non-blocking stream, which is ordered with NO other stream — not with the NULL stream, not with
+ * torch's current stream.  There, the producer of device-resident queries, probes, bitmaps and of the initial contents of the
+ * output buffers must have FINISHED (hipStreamSynchronize / torch.cuda.synchronize) before an MDB_MEM_DEVICE call is made, and
+ * mdb_sync must have returned before anyone reads the outputs.
+ *
+ * On a BORROWED stream an MDB_MEM_DEVICE call is one more piece of work on that stream and needs no synchronisation at all:
+ *   - everything the call does on the device is enqueued on that stream and on no other, so work enqueued there before the call
+ *     (the copy or kernel that produces the queries) is seen by it, and work enqueued behind it sees its outputs;
+ *   - the query rows, device probes and device bitmaps are read by that enqueued work (small aligned batches in place, with no
+ *     staging copy): they may be overwritten or freed by work enqueued on the SAME stream behind the call, and by nothing else
+ *     until the stream has passed the call;
+ *   - host arrays that accompany such a call (user ids, mdb_search_params, the quantizer descriptor) are consumed before the
+ *     call returns and may be reused at once;
+ *   - the call returns without waiting for the stream, with these exceptions: mdb_pq_quantize_mem, mdb_ivf_assign and
+ *     mdb_kmeans_fit wait inside; the fifth of five calls that each stage a host array (mdb_multi_spann_search: four pinned
+ *     slots) waits for the first one's copy; a call that outgrows the context's scratch makes the NEXT call wait for the stream
+ *     once while the scratch is consolidated.
+ * tests/test_gpu_async_stream.py holds all of this, on a side stream and on the NULL stream, with the host ahead of the GPU. */
 mdb_status mdb_set_stream(mdb_ctx* ctx, void* hip_stream);
-/* wait for the stream; returns the first deferred error of MDB_MEM_DEVICE calls (e.g. MDB_ERR_NAN) */
+/* wait for the stream; returns the first deferred error of the MDB_MEM_DEVICE calls since the last synchronising call (e.g.
+ * MDB_ERR_NAN: such a call itself returns MDB_OK), once — the next mdb_sync returns MDB_OK.  The rows of other calls, issued
+ * before or behind the failing one, are not affected.  A deferred error that has not been collected is reported by the next
+ * call that synchronises (any MDB_MEM_HOST call, or a *_submit through its mdb_wait): call mdb_sync first to keep them apart.
+ * The status of a PENDING *_submit is not mdb_sync's to report: it stays with mdb_wait, whichever of the two is called first. */
 mdb_status mdb_sync(mdb_ctx* ctx);
 /* completes the context's pending mdb_*_search_submit call (no-op without one): waits for the stream, copies the results
  * into the caller's buffers given at submit time and returns the call's status */

@@ -114,7 +114,7 @@ struct mdb_ctx {
     mdb_status deferred = MDB_OK;
     mdb_stats stats{};
     uint32_t* d_flags = nullptr;   // device word: bit0 NaN seen, bit1 capacity overflow
-    uint32_t* h_flags = nullptr;   // pinned host mirror
+    uint32_t* h_flags = nullptr;   // pinned host mirror, two words: [0] mdb_check_flags (synchronising calls, mdb_sync), [1] the pending *_submit (mdb_wait)
     unsigned long long* d_counters = nullptr;  // 32 words; [0] HNSW distance evals [1] expanded nodes [2] scored vectors [3] spare (words 4..15: debug
                                                // builds); words 16..19 / 20..23: the fused IVF-PQ step alternates between them — each call's kernel clears the
                                                // OTHER set for the next call, so the step needs no memset launch

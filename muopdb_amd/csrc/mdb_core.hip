@@ -94,7 +94,8 @@ mdb_status mdb_return_to_host(mdb_ctx* ctx, const HostCopy* items, int n) {
             ctx->pending.push_back({items[i].dst, off, items[i].bytes});
             off += align_up(items[i].bytes, 64);
         }
-        MDB_HIP(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+        // into the pending call's OWN host word: an MDB_MEM_DEVICE call + mdb_sync between submit and wait reuse h_flags[0]
+        MDB_HIP(ctx, hipMemcpyAsync(ctx->h_flags + 1, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
         MDB_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, 4, ctx->stream));
         ctx->has_pending = true;
         return MDB_OK;
@@ -119,7 +120,7 @@ extern "C" mdb_status mdb_wait(mdb_ctx* ctx) {
     const char* stage = (const char*)ctx->pinned[MDB_PIN_OUT];
     for (auto& c : ctx->pending) memcpy(c.dst, stage + c.off, c.bytes);
     ctx->pending.clear();
-    return flags_to_status(ctx, *ctx->h_flags);
+    return flags_to_status(ctx, ctx->h_flags[1]);
 }
 
 extern "C" int mdb_poll(mdb_ctx* ctx) {
@@ -171,7 +172,7 @@ mdb_status mdb_device_open(int gpu, mdb_ctx** out) {
         (void)hipFree(p);
     };
     if (hipSetDevice(gpu) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&ctx->d_flags, 4) != hipSuccess || hipHostMalloc((void**)&ctx->h_flags, 4) != hipSuccess ||
+        hipMalloc((void**)&ctx->d_flags, 4) != hipSuccess || hipHostMalloc((void**)&ctx->h_flags, 8) != hipSuccess ||
         hipMemset(ctx->d_flags, 0, 4) != hipSuccess || hipMalloc((void**)&ctx->d_counters, 256) != hipSuccess ||
         hipHostMalloc((void**)&ctx->h_counters, 256) != hipSuccess || hipMemset(ctx->d_counters, 0, 256) != hipSuccess) {
         delete ctx;

@@ -17,14 +17,26 @@ QUANT_NONE, QUANT_PQ = 0, 1
 PQ_SCALAR, PQ_SIMD, PQ_STREAMING = 0, 1, 2
 
 
+def _up_to_date():
+    return os.path.exists(_SO) and os.path.exists(_SRC) and os.path.getmtime(_SO) >= os.path.getmtime(_SRC)
+
+
 def build(force=False):
-    """Compile the oracle with g++ (oracle/Makefile).  No-op when the .so is up to date."""
-    if (not force and os.path.exists(_SO) and os.path.exists(_SRC)
-            and os.path.getmtime(_SO) >= os.path.getmtime(_SRC)):
+    """Compile the oracle with g++ (oracle/Makefile).  No-op when the .so is up to date.  Processes that find it stale at the
+    same time (the spawned ranks of the gloo tests) build one after the other — the second finds it done — and the Makefile
+    renames the finished library into place, so nobody ever loads a file that is still being written."""
+    if not force and _up_to_date():
         return _SO
     if not os.path.exists(_SRC):
         return _SO
-    subprocess.check_call(["make", "-C", _HERE, "-B" if force else "-s"])
+    import fcntl
+    fd = os.open(_HERE, os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        if force or not _up_to_date():
+            subprocess.check_call(["make", "-C", _HERE, "-B" if force else "-s"])
+    finally:
+        os.close(fd)
     return _SO
 
 

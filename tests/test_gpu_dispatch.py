@@ -489,6 +489,7 @@ def test_spann_device_calls_without_fused_remap(ctx, oracle, spann_case):
         sc = torch.zeros((b, k), dtype=torch.float32, device=dev)
         cn = torch.zeros(b, dtype=torch.int32, device=dev)
         fo = torch.zeros(b, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()   # the upload and the fills run on torch's stream, the search on the context's
         ctx.check(ctx.lib.mdb_multi_spann_search(ms.h, L_.u128_array(users), C.c_void_p(qd.data_ptr()), C.c_size_t(b), C.byref(pc),
                                                  C.c_int(L_.MEM_DEVICE), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()),
                                                  C.c_void_p(cn.data_ptr()), C.c_void_p(fo.data_ptr())))

@@ -25,6 +25,7 @@ def _flat_device(ctx, g, qd, b, k):
     ids = torch.full((b, k), -1, dtype=torch.int32, device=dev)
     dist = torch.zeros((b, k), dtype=torch.float32, device=dev)
     cnt = torch.zeros(b, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()   # the fills (and qd) are torch's stream's work; the context runs on its own, not ordered with it
     g.search_device(qd.data_ptr(), b, k, ids.data_ptr(), dist.data_ptr(), cnt.data_ptr())
     ctx.sync()
     return ids.cpu().numpy().view(np.uint32), dist.cpu().numpy(), cnt.cpu().numpy().view(np.uint32)
@@ -135,6 +136,7 @@ def test_ivf_and_spann_device_rows_in_place(ctx, oracle):
         ids = torch.zeros((b, k, 2), dtype=torch.int64, device=dev)
         sc = torch.zeros((b, k), dtype=torch.float32, device=dev)
         cn = torch.zeros(b, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()   # torch's stream is not ordered with the context's
         ctx.check(ctx.lib.mdb_ivf_search(g.h, C.c_void_p(qd.data_ptr()), C.c_size_t(b), None, C.c_size_t(P), C.c_size_t(k),
                                          C.c_int(L_.MEM_DEVICE), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cn.data_ptr())))
         ctx.sync()
@@ -162,6 +164,7 @@ def test_ivf_and_spann_device_rows_in_place(ctx, oracle):
         sc = torch.zeros((b, k), dtype=torch.float32, device=dev)
         cn = torch.zeros(b, dtype=torch.int32, device=dev)
         fo = torch.zeros(b, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()   # torch's stream is not ordered with the context's
         ctx.check(ctx.lib.mdb_spann_search(sp.h, C.c_void_p(qd.data_ptr()), C.c_size_t(b), C.byref(pc), C.c_int(L_.MEM_DEVICE),
                                            C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cn.data_ptr()),
                                            C.c_void_p(fo.data_ptr())))

@@ -495,6 +495,7 @@ def test_hnsw_refusals_leave_the_handle_usable(ctx, hnsw6000):
                 UNSUPPORTED, text)
         ctx.sync()                                                                # decided on the host: no deferred status
         ids, sc, cn, _ = device_rows(torch, len(q), 10)
+        torch.cuda.synchronize()   # torch's fills are not ordered with the context's stream
         g.ann_search_device(qd.data_ptr(), len(q), 10, 600, ids.data_ptr(), sc.data_ptr(), cn.data_ptr())
         ctx.sync()
         assert_result_rows(rows_to_result(len(q), 10, ids, sc, cn), o.ann_search(q, 10, 600), len(q))

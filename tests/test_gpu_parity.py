@@ -489,6 +489,7 @@ def test_ivf_pq_fused_step(ctx, oracle, n, d, sub, L, P, k):
     ids = torch.zeros((b, k, 2), dtype=torch.int64, device=dev)
     sc = torch.zeros((b, k), dtype=torch.float32, device=dev)
     cn = torch.zeros(b, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()   # the upload and the fills run on torch's stream, the search on the context's
     ctx.check(ctx.lib.mdb_ivf_search(g.h, C.c_void_p(qd.data_ptr()), C.c_size_t(b), None, C.c_size_t(P), C.c_size_t(k), C.c_int(L_.MEM_DEVICE),
                                      C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(cn.data_ptr())))
     ctx.sync()

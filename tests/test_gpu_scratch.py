@@ -208,6 +208,7 @@ def test_ivf_assign_second_pass_of_the_loop(ctx, assign_case, mem):
         cd, vd = torch.from_numpy(cent).to(dev), torch.from_numpy(v).to(dev)
         idd = torch.zeros((n, mc), dtype=torch.int32, device=dev)
         cnd = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()   # the uploads and fills run on torch's stream, the call on the context's
         ctx.check(ctx.lib.mdb_ivf_assign(ctx.h, C.c_void_p(cd.data_ptr()), C.c_size_t(cent.shape[0]), C.c_void_p(vd.data_ptr()), C.c_size_t(n),
                                          C.c_size_t(d), C.c_size_t(mc), C.c_float(thr), C.c_int(L.MEM_DEVICE),
                                          C.c_void_p(idd.data_ptr()), C.c_void_p(cnd.data_ptr())))

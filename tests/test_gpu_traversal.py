@@ -906,6 +906,7 @@ def test_user_and_batch_partitionings_on_the_device(ctx, oracle, world):
         ms = MultiSpannIndex(ctx, table[D.users_of_rank(U, r, world)].tobytes(), *a)
         assert ms.num_users() == len(D.users_of_rank(U, r, world))
         ql = ex.local_queries(qd).contiguous()
+        torch.cuda.synchronize()   # the exchange's buffers and the routed rows are torch's stream's work, the search runs on the context's
         if ex.n_local:
             ctx.check(ctx.lib.mdb_multi_spann_search(ms.h, L.u128_array([uids[i] for i in routes[r]]), C.c_void_p(ql.data_ptr()), C.c_size_t(ex.n_local),
                                                      C.byref(pc), C.c_int(L.MEM_DEVICE), C.c_void_p(ex.ids.data_ptr()), C.c_void_p(ex.scores.data_ptr()),
@@ -945,6 +946,7 @@ def test_user_and_batch_partitionings_on_the_device(ctx, oracle, world):
         ex = D.RowsExchange(b, k, routes2, r, "cuda")
         ql = ex.local_queries(q2d)
         assert ex.contiguous and ql.data_ptr() == q2d.data_ptr() + routes2[r][0] * 32 * 4     # a view: the rows are read in place
+        torch.cuda.synchronize()   # torch's stream is not ordered with the context's
         ctx.check(ctx.lib.mdb_ivf_search(ivf.h, C.c_void_p(ql.data_ptr()), C.c_size_t(ex.n_local), None, C.c_size_t(5), C.c_size_t(k),
                                          C.c_int(L.MEM_DEVICE), C.c_void_p(ex.ids.data_ptr()), C.c_void_p(ex.scores.data_ptr()),
                                          C.c_void_p(ex.counts.data_ptr())))
