@@ -78,7 +78,10 @@ def kmeans_fit(ctx, x, num_clusters, max_iter=10, tolerance=0.0, init_ids=None, 
 
 
 def kmeans(ctx, x, k, iters=10, seed=0, sample=None, tolerance=0.0):
-    """centroids [k][d] of a (sampled) Lloyd run — IvfBuilder's use of KMeansBuilder (ivf/builder.rs:470-500)."""
+    """centroids [k][d] of a (sampled) Lloyd run — IvfBuilder's use of KMeansBuilder (ivf/builder.rs:470-500).
+    Draws (the contract tests/build_model.py restates): with sample < n the rows are
+    sort(default_rng(seed + 7919).choice(n, sample, replace=False)); the initial points are kmeans_fit's
+    default_rng(seed).choice(n', min(k, n'), replace=False) over the n' rows that are left."""
     n = x.shape[0]
     if sample is not None and sample < n:
         x = _take(x, np.sort(np.random.default_rng(seed + 7919).choice(n, size=sample, replace=False)))
@@ -86,7 +89,11 @@ def kmeans(ctx, x, k, iters=10, seed=0, sample=None, tolerance=0.0):
 
 
 def train_pq_codebook(ctx, x, subdim, num_bits, iters=8, seed=0, sample=100_000):
-    """[m][2^num_bits][subdim] f32 codebook, flattened (the `codebook` file of pq/mod.rs:101-126): one k-means per subvector."""
+    """[m][2^num_bits][subdim] f32 codebook, flattened (the `codebook` file of pq/mod.rs:101-126): one k-means per subvector.
+    Draws (the contract tests/build_model.py restates): with sample < n the rows are
+    sort(default_rng(seed + 104729).choice(n, sample, replace=False)); subvector s starts from
+    default_rng(seed + s).choice(n', min(K, n'), replace=False) over the n' rows that are left, K = 2^num_bits; a run
+    that returns fewer than K rows (n' < K) is padded with copies of its last row."""
     n, d = x.shape
     m, K = d // subdim, 1 << num_bits
     if sample is not None and sample < n:
@@ -210,7 +217,13 @@ def ivf_build_centroids(ctx, x, num_clusters, max_posting_list_size, num_data_po
     (cluster_docs :419-444: ceil(len / max) clusters from a sample of max(10 * clusters, num_data_points_for_clustering) of
     its points) until no list exceeds max_posting_list_size.  Returns (centroids [L][d] numpy, posting lists as sorted u64
     arrays); empty lists are dropped like the reference does (:529-534).  The reference's sampling is thread_rng, so the
-    outcome is quality-parity; each k-means run inside is the bit-exact mdb_kmeans_fit."""
+    outcome is quality-parity; each k-means run inside is the bit-exact mdb_kmeans_fit.
+    Draws (the contract tests/build_model.py restates): ONE default_rng(seed) serves every sample pick, in call order — a
+    call samples only when its list is longer than the sample size, sort(rng.choice(point ids, size, replace=False)).  Lists
+    are numbered in the order they are produced (`tick`); the k-means of a call starts from
+    default_rng(seed + tick).choice(n', min(k, n'), replace=False), tick = the number of lists produced before the call
+    (0 for the first pass).  The longest list is split next, the earliest-numbered among equally long ones; the result lists
+    the surviving non-empty lists by number."""
     import heapq
     n, d = x.shape
     rng = np.random.default_rng(seed)
@@ -287,6 +300,23 @@ def insert_hnsw(ctx, x, max_neighbors=32, max_layers=8, ef_construction=100, see
     and the first `exact_below` points take their candidates from an exact scan (FlatIndex) instead of a graph search.
     The reference stores the heuristic's NEGATED distance on a kept edge (builder.rs:366-369, a sign slip that its later
     trims inherit); edges here carry the true distance.
+
+    The build is a function of (x, max_neighbors = M, max_layers, ef_construction, seed, batch_frac, exact_below) alone, and
+    tests/build_model.py restates it point by point; the two give the same edge lists in the same order.  Its rules:
+    * levels: u = 1 - default_rng(seed).random(n), level = min(floor(-ln u / ln M), max_layers); point 0 is there from the
+      start; a batch is the next min(n - cur, max(1, int(cur * batch_frac))) points, cur = points inserted so far;
+    * layer-0 candidates: the exact top min(ef_construction, cur) among the points before the batch while
+      cur <= exact_below, afterwards ann_search(min(ef_construction, cur), ef_construction) over the graph as of cur; they
+      enter the heuristic in pop order (distance ascending, larger id first among equals); the kept list, in kept order,
+      is the new point's edge list;
+    * layer-0 reverse edges, per old target: its newcomers are ordered by (distance ascending, new point id ascending);
+      if they all fit they are appended in that order; otherwise the target's whole list, with its stored distances, and
+      only the first 2M newcomers go through the heuristic in pop order, and the result replaces the list;
+    * upper layers: candidates are the exact top min(ef_construction, members) among the layer's members before the batch;
+      reverse edges are appended in ascending order of the new point (not by distance); a list that exceeds M is trimmed
+      once, whole (no 2M cap), after the batch is linked on that layer; a point that opens a layer gets an empty list;
+    * when a batch raises the top layer, its lowest point of the new highest level becomes the entry point, written first
+      in the top layer (batches go in id order, so that point is the layer's lowest id and every layer is ascending).
 
     x: [n][d] numpy or torch CUDA tensor.  Returns (layers, levels): layers in formats.write_hnsw_index's CSR form
     (layer 0 first; points None for layer 0), point ids = row numbers."""

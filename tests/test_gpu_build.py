@@ -296,7 +296,10 @@ def test_select_neighbors_heuristic(ctx, oracle):
 def test_insert_hnsw_quality_parity_with_the_reference_algorithm(ctx, oracle):
     """SURVEY.md §8f rank 3: the batched GPU construction (muopdb_amd.build.insert_hnsw: HnswBuilder::insert's steps over the
     library's traversal + selection kernels) against the oracle's sequential restatement of HnswBuilder::insert on the same
-    points and parameters: recall@10 of the two graphs under the same search, degree bound, every point reachable."""
+    points and parameters: recall@10 of the two graphs under the same search, degree bound, every point reachable.
+    This is the RECALL check of the batching relaxation (points of one batch do not see each other) at a realistic size; it
+    cannot see a slip that costs a fraction of a percent.  The edge lists themselves are pinned in
+    tests/test_gpu_build_exact.py against the point-by-point model of tests/build_model.py."""
     from muopdb_amd import build as B
     from muopdb_amd import formats as F
     from muopdb_amd.index import BlockBasedHnsw, FlatIndex
