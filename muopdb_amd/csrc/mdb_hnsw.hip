@@ -747,19 +747,6 @@ __host__ __device__ constexpr int beam_block(bool l0) { return l0 ? MDB_HNSW_L0_
 __host__ __device__ constexpr int beam_lds_c(int nb) { return nb <= 5 ? 2048 : 4096; }
 __host__ __device__ constexpr int beam_lds_qs(int nb) { return beam_lds_c(nb) + 8192 + 1024 + 1024 + 64; }
 
-#ifdef MDB_PIPE_DBG   // cycle / event accounting of the roles into counters[4..15] (MDB_HNSW_DBG=1 prints them): cycles of P2 | barrier |
-// shadow (selection) | barrier | P4, steps, steps with > 12 / > 24 / > 28 new neighbours, a distance wave's phase, compactions by bound / by select.
-// hnsw_upper_kernel (mdb_hnsw_upper.hip) adds ITS phases and counts into the same words (slots 6-8 there: new neighbours, survivors,
-// accepted; 10 / 11: compactions by bound / by select, as here): build one of the two files with the flag at a time
-#define PIPE_TB(t) const unsigned long long t = __builtin_readcyclecounter()
-#define PIPE_TE(slot, t) dbg_acc[slot] += __builtin_readcyclecounter() - (t)
-#define PIPE_CNT(slot, v) dbg_acc[slot] += (v)
-#else
-#define PIPE_TB(t) do {} while (0)
-#define PIPE_TE(slot, t) do {} while (0)
-#define PIPE_CNT(slot, v) do {} while (0)
-#endif
-
 // ROW64: every adjacency row of the index has at most 64 edges (max_neighbors <= 32: the configurations' graphs) — a row is ONE
 // register per lane, a step has ONE chunk: the per-chunk loops, their scalar branches and three of four register copies leave
 // wave 0's chain.
@@ -940,7 +927,7 @@ __global__ __launch_bounds__(beam_block(L0)) void hnsw_beam_kernel(HnswArgs a) {
         }
         for (;;) {
             // ---- P2 (wave 0): visited test-and-set + ordered compaction of the popped node's row
-            PIPE_TB(t_p2);
+            PIPE_T(t_p2);
             if (wave == 0) {
                 uint32_t nnew = 0xFFFFFFFFu;
                 if (!stop && !overflow) {
@@ -968,10 +955,10 @@ __global__ __launch_bounds__(beam_block(L0)) void hnsw_beam_kernel(HnswArgs a) {
                 if (lane == 0) misc[0] = nnew;
             }
             if (wave == 0) PIPE_TE(0, t_p2);
-            PIPE_TB(t_b1);
+            PIPE_T(t_b1);
             __syncthreads();
             if (wave == 0) PIPE_TE(1, t_b1);
-            PIPE_TB(t_sh);
+            PIPE_T(t_sh);
             // the groups' FIRST neighbour is fetched before the list length is known: nb_id[group] and then the vector are requested
             // right behind the barrier, in parallel with the read of misc[0] (slots past the list hold ids of earlier steps — valid
             // rows, their values unused); the length used to sit in front of both round trips
@@ -1071,10 +1058,10 @@ __global__ __launch_bounds__(beam_block(L0)) void hnsw_beam_kernel(HnswArgs a) {
             }
             if (wave == 0) PIPE_TE(2, t_sh);
             if (wave == 1) PIPE_TE(9, t_sh);
-            PIPE_TB(t_b2);
+            PIPE_T(t_b2);
             __syncthreads();
             if (wave == 0) PIPE_TE(3, t_b2);
-            PIPE_TB(t_p4);
+            PIPE_T(t_p4);
             // ---- P4 (wave 0): accept + push, then choose the next node
             if (wave == 0) {
                 uint32_t best_o = SLOT_EMPTY, best_id = 0;  // best accepted neighbour in pop order

@@ -358,7 +358,7 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
             evals += 1;
         }
         while (true) {
-            UP_T(t0);
+            PIPE_T(t0);
             // ---- the runner-up (the nearest candidate already in U: the next pop unless a neighbour accepted below beats it) ...
             const uint32_t ru = bm_find_first<NW>(U, sU);
             uint32_t pu = 0;
@@ -376,7 +376,7 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
                 ru_ok = !(pu >> 15);                    // an exact tie with the next rank: the pop below resolves it the long way
                 if (ru_ok) rowr = load_row(pu & 0x7FFFu);
             }
-            UP_T(t1);
+            PIPE_T(t1);
             const bool have = valid && !(old & bit);
             const unsigned long long hm = __ballot(have);
             const uint32_t nnew = (uint32_t)__popcll(hm);
@@ -384,13 +384,13 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
             evals += nnew;
             const uint32_t rk = rv & 0x7FFFu;
             if (__ballot(have && rk >= nan_start)) nan_seen = true;   // the reference panics (NotNan::new(..).unwrap())
-            UP_T(t2);
-            UP_ACC(0, t1 - t0); UP_ACC(1, t2 - t1); UP_ACC(5, 1); UP_CNT(6, nnew);
+            PIPE_T(t2);
+            PIPE_ACC(0, t1 - t0); PIPE_ACC(1, t2 - t1); PIPE_ACC(5, 1); PIPE_CNT(6, nnew);
             if (nnew) {
                 // ---- acceptance in edge order: `d_e < furthest.d || len < ef`, then push + evict (index.rs:262-281)
                 unsigned long long surv = len >= ef ? __ballot(have && rk < rf) : hm;
                 const unsigned long long tnm = __ballot(have && (rv >> 15));
-                UP_CNT(7, __popcll(surv));
+                PIPE_CNT(7, __popcll(surv));
                 while (surv) {
                     const int s = __builtin_ctzll(surv);
                     surv &= surv - 1;
@@ -406,11 +406,11 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
                         rf = bm_find_prev<NW>(A, sA, rf);                                         // working_list.pop(): the furthest leaves W
                     }
                     bm_set<NW>(U, sU, r, lane);
-                    UP_CNT(8, 1);
+                    PIPE_CNT(8, 1);
                 }
             }
-            UP_T(t3);
-            UP_ACC(2, t3 - t2);
+            PIPE_T(t3);
+            PIPE_ACC(2, t3 - t2);
             // ---- candidates.pop(): lowest distance, the LARGEST id among its exact ties
             uint32_t r0 = bm_find_first<NW>(U, sU);
             if (r0 == RK_NONE) break;
@@ -433,8 +433,8 @@ __device__ __forceinline__ void upper_traverse_rank(const HnswUpArgs& a, const i
             if (r0 > rf && !rank_tied(P, rf, r0)) break;
             bm_clear_bit<NW>(U, sU, r0, lane);
             rowv = predicted ? rowr : load_row(c0);
-            UP_T(t4);
-            UP_ACC(3, t4 - t3);
+            PIPE_T(t4);
+            PIPE_ACC(3, t4 - t3);
         }
         // ---- a layer hands its nearest point down (index.rs:177-181: smallest distance, then smallest id) = the lowest rank in A
         ep = rk_first((uint32_t)P[bm_find_first<NW>(A, sA)]) & 0x7FFFu;
@@ -575,7 +575,7 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
         uint32_t uL = 0, uw = 0;
         bool plain = false;
         while (true) {
-            UP_T(t0);
+            PIPE_T(t0);
             // ---- the runner-up: the next set bit behind the popped one (the next pop unless a neighbour accepted below beats it)
             uint32_t ru = RK_NONE, pu = 0;
             if (__builtin_expect(plain, 0)) {
@@ -607,7 +607,7 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
                 ru_ok = !(pu >> 15);                    // an exact tie with the next rank: the pop below resolves it the long way
                 if (ru_ok) rowr = load_row(pu & 0x7FFFu);
             }
-            UP_T(t1);
+            PIPE_T(t1);
             const bool have = valid && !(old & bit);
             const unsigned long long hm = __ballot(have);
             const uint32_t nnew = (uint32_t)__popcll(hm);
@@ -615,8 +615,8 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
             evals += nnew;
             const uint32_t rk = rv & 0x7FFFu;
             nanm |= __ballot(have && rk >= nan_start);                 // the reference panics (NotNan::new(..).unwrap())
-            UP_T(t2);
-            UP_ACC(0, t1 - t0); UP_ACC(1, t2 - t1); UP_ACC(5, 1); UP_CNT(6, nnew);
+            PIPE_T(t2);
+            PIPE_ACC(0, t1 - t0); PIPE_ACC(1, t2 - t1); PIPE_ACC(5, 1); PIPE_CNT(6, nnew);
             if (hm) {
                 if (len + (int)nnew <= ef) {
                     // ---- fill phase: `len < ef` accepts every new neighbour, nothing is evicted
@@ -633,14 +633,14 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
                     const unsigned long long am = __ballot(A != 0u);
                     const uint32_t La = 63u - (uint32_t)__builtin_clzll(am);
                     rf = (La << 5) | (31u - (uint32_t)__builtin_clz(rk_readlane(A, La)));
-                    UP_CNT(8, nnew);
-                    UP_T(tf);
-                    UP_ACC(11, tf - t2); UP_ACC(4, 1);
+                    PIPE_CNT(8, nnew);
+                    PIPE_T(tf);
+                    PIPE_ACC(11, tf - t2); PIPE_ACC(4, 1);
                 } else {
                     // ---- acceptance in edge order: `d_e < furthest.d || len < ef`, then push + evict (index.rs:262-281)
                     unsigned long long surv = len >= ef ? __ballot(have && rk < rf) : hm;
                     const unsigned long long tnm = __ballot(have && (rv >> 15));
-                    UP_CNT(7, __popcll(surv));
+                    PIPE_CNT(7, __popcll(surv));
                     while (surv) {
                         const int s = __builtin_ctzll(surv);
                         surv &= surv - 1;
@@ -667,12 +667,12 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
                             const uint32_t L2 = 63u - (uint32_t)__builtin_clzll(m);
                             rf = (L2 << 5) | (31u - (uint32_t)__builtin_clz(rk_readlane(A, L2)));
                         }
-                        UP_CNT(8, 1);
+                        PIPE_CNT(8, 1);
                     }
                 }
             }
-            UP_T(t3);
-            UP_ACC(2, t3 - t2);
+            PIPE_T(t3);
+            PIPE_ACC(2, t3 - t2);
             // ---- candidates.pop(): lowest distance, the LARGEST id among its exact ties
             um = __ballot(U != 0u);
             if (!um) break;
@@ -702,8 +702,8 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
             }
             U &= ~((uint32_t)lane == (r0 >> 5) ? 1u << (r0 & 31) : 0u);
             rowv = predicted ? rowr : load_row(c0);
-            UP_T(t4);
-            UP_ACC(3, t4 - t3);
+            PIPE_T(t4);
+            PIPE_ACC(3, t4 - t3);
         }
         // ---- a layer hands its nearest point down (index.rs:177-181: smallest distance, then smallest id) = the lowest rank in A
         {

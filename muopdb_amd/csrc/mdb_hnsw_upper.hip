@@ -291,35 +291,14 @@ struct HnswUpArgs {
     int dbg_on;               // MDB_PIPE_DBG builds: this launch adds its cycle sums to counters[4..15] (MDB_HNSW_DBG bit 0: bottom launch, bit 1: top)
 };
 
-#ifdef MDB_PIPE_DBG   // -DMDB_PIPE_DBG + MDB_HNSW_DBG=1: cycle / event sums into counters[4..15] (the traversal kernels print the same words)
-#define UP_T(t) const unsigned long long t = __builtin_readcyclecounter()
-#define UP_ACC(slot, v) dbg_acc[slot] += (v)
-#if MDB_PIPE_DBG >= 2   // finer split of selection and pop into slots 6..11 (instead of the event counts); the row wait made explicit
-#define UP_T2(t) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long t = __builtin_readcyclecounter()
-#define UP_T2L(t) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t = __builtin_readcyclecounter()
-#define UP_ACC2(slot, v) dbg_acc[slot] += (v)
-#define UP_CNT(slot, v) do {} while (0)
-#else
-#define UP_T2(t) do {} while (0)
-#define UP_T2L(t) do {} while (0)
-#define UP_ACC2(slot, v) do {} while (0)
-#define UP_CNT(slot, v) dbg_acc[slot] += (v)
-#endif
-#else
-#define UP_T2(t) do {} while (0)
-#define UP_T2L(t) do {} while (0)
-#define UP_ACC2(slot, v) do {} while (0)
-#define UP_CNT(slot, v) do {} while (0)
-#define UP_T(t) do {} while (0)
-#define UP_ACC(slot, v) do {} while (0)
-#endif
 #define UP_LDS_STAGE 0                 // 512 keys (compaction staging)
 #define UP_LDS_FLAG 4096               // 512 words
 #define UP_LDS_FR 6144                 // two frontier lists of 64 (closure of tiny layers)
 #define UP_LDS_VIS 6656
 
-// One wave per query.  State and step logic are hnsw_beam_kernel's wave 0 (over-full unsorted register beam B, acceptance and stop
-// test by counting, runner-up + its row fetched ahead); what is gone is everything between its P2 and P4.
+// One wave per query.  The state is the Beam<NB> of mdb_hnsw_dev.hip.h and the step a sequence of its operations (over-full
+// unsorted register beam B, acceptance and stop test by counting, runner-up + its row fetched ahead) — the step hnsw_beam_kernel's
+// wave 0 runs, written out there; what is gone is everything between its P2 and P4.
 // TLDS: the query's table row (nu_pad words, 129 KB at 1 M points / 32 k upper points) is copied into LDS by the whole block first —
 // a lookup is then an LDS read (~100 cycles) instead of a first-touch miss of a line the table kernel wrote from another XCD
 // (the L2s are not coherent: the row comes back from the Infinity Cache / HBM, ~1 k cycles, 40 % of the lookups).  Waves 1-3 only
@@ -344,16 +323,12 @@ __device__ __forceinline__ void upper_traverse_wave0(const HnswUpArgs& a, const 
     const int ef = a.ef;
     const uint32_t su = a.su;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    uint32_t bd[NB], bi[NB], cdv[NB];
-    int n = 0;
-    uint32_t fbound = SLOT_EMPTY;
+    Beam<NB> B;   // the register beam (mdb_hnsw_dev.hip.h): seeded at every layer's entry point
     uint32_t rowv = 0xFFFFFFFFu, rowr = 0xFFFFFFFFu;
-    uint32_t ru_o = SLOT_EMPTY, ru_id = 0;
-    bool ru_valid = false, stop = false, overflow = a.in_ovf ? a.in_ovf[qi] != 0u : false, nan_lane = false;
+    BeamCand ru = {SLOT_EMPTY, 0, false};   // the runner-up: the best candidate already in B
+    bool stop = false, overflow = a.in_ovf ? a.in_ovf[qi] != 0u : false, nan_lane = false;
     int ru_closer = 0;
-    // expanded slots of B.  Every unexpanded slot is at least as far as the candidate about to be popped, so the stop count
-    // #{b : d_b < d_candidate} is at most nexp: no count is taken while nexp < ef (a layer stops after >= ef expansions or not at all)
-    int nexp = 0;
+    int nexp = 0;   // expanded slots of B: no stop count is taken while nexp < ef (see beam_pop)
     uint32_t evals = a.in_cnt ? a.in_cnt[4 * qi + 0] : 0u, expanded = a.in_cnt ? a.in_cnt[4 * qi + 1] : 0u;
     if (a.in_cnt && a.in_cnt[4 * qi + 2]) nan_lane = true;
     uint32_t ep = a.in_ep ? a.in_ep[qi] : a.entry_c;
@@ -417,19 +392,15 @@ __device__ __forceinline__ void upper_traverse_wave0(const HnswUpArgs& a, const 
             const uint32_t od0 = tq[ep];
             const float f0 = f32_from_orderable(od0);
             if (f0 != f0) nan_lane = true;
-#pragma unroll
-            for (int r = 0; r < NB; ++r) { bd[r] = SLOT_EMPTY; bi[r] = 0; cdv[r] = SLOT_EMPTY; }
-            if (lane == 0) { bd[0] = od0; bi[0] = ep; }
-            n = 1;
+            B = beam_seed<NB>(ep, od0, lane);
             nexp = 1;
-            fbound = SLOT_EMPTY;
             stop = false;
-            ru_valid = false;
+            ru.have = false;
             evals += 1;
         }
         while (!stop && !overflow) {
             // ---- visited test-and-set and table lookups of the popped node's row: issued together ...
-            UP_T(t0);
+            PIPE_T(t0);
             const uint32_t nbr = (uint32_t)lane < su ? rowv : 0xFFFFFFFFu;
             const bool valid = nbr != 0xFFFFFFFFu;
             const uint32_t bit = 1u << (nbr & 31);
@@ -437,19 +408,15 @@ __device__ __forceinline__ void upper_traverse_wave0(const HnswUpArgs& a, const 
             uint32_t od = tq[valid ? nbr : 0u];
             // ---- ... and in flight while the wave finds the best candidate already in B (the next pop unless a neighbour accepted
             // below beats it), requests its row and takes its stop count
-            UP_T2L(s0);   // (debug 2: the LDS round trip of the visited set / table is retired here, not behind the selection)
-            ru_valid = beam_best_id(cdv, bi, ru_o, ru_id);
-            UP_T2L(s1);
-            if (ru_valid) {
-                rowr = load_row(ru_id);
-                ru_closer = 0;
-                if (nexp >= ef) {
-#pragma unroll
-                    for (int r = 0; r < NB; ++r) ru_closer += __popcll(__ballot(bd[r] < ru_o));
-                }
+            PIPE_T2L(s0);   // (debug 2: the LDS round trip of the visited set / table is retired here, not behind the selection)
+            ru = beam_select(B);
+            PIPE_T2L(s1);
+            if (ru.have) {
+                rowr = load_row(ru.id);
+                ru_closer = nexp >= ef ? beam_count_closer(B, ru.o) : 0;
             }
-            UP_T(t1);
-            UP_ACC2(6, s0 - t0); UP_ACC2(7, s1 - s0);
+            PIPE_T(t1);
+            PIPE_ACC2(6, s0 - t0); PIPE_ACC2(7, s1 - s0);
             const bool have = valid && !(old & bit);
             const unsigned long long hm = __ballot(have);
             const uint32_t nnew = (uint32_t)__popcll(hm);
@@ -461,164 +428,55 @@ __device__ __forceinline__ void upper_traverse_wave0(const HnswUpArgs& a, const 
                 if (fd != fd) nan_lane = true;   // the reference panics (NotNan::new(..).unwrap())
             }
             const uint32_t id = nbr;
-            // ---- accept + push (hnsw_beam_kernel P4 on row lanes), then choose the next node
-            uint32_t best_o = SLOT_EMPTY, best_id = 0;
-            bool best_have = false;
-            UP_T(t2);
-            UP_ACC(0, t1 - t0); UP_ACC(1, t2 - t1); UP_ACC(5, 1); UP_CNT(6, nnew);
+            // ---- accept + push, then choose the next node
+            BeamCand best = {SLOT_EMPTY, 0, false};   // best accepted neighbour in pop order
+            PIPE_T(t2);
+            PIPE_ACC(0, t1 - t0); PIPE_ACC(1, t2 - t1); PIPE_ACC(5, 1); PIPE_CNT(6, nnew);
             if (nnew) {
-                unsigned long long surv = __ballot(have && od < fbound);
-                UP_CNT(7, __popcll(surv));
-                unsigned long long accepted = 0;
-                // fill phase of a layer: B still holds at most ef elements after this step — every count below would be < ef
-                if (n + (int)nnew <= ef) { accepted = surv; surv = 0; }
-                while (surv) {
-                    const int sidx = __ffsll((long long)surv) - 1;
-                    surv &= surv - 1;
-                    const uint32_t ds = (uint32_t)__builtin_amdgcn_readlane((int)od, sidx);
-                    int cnt = __popcll(__ballot(have && od <= ds) & ((1ull << sidx) - 1ull));
-#pragma unroll
-                    for (int r = 0; r < NB; ++r) cnt += __popcll(__ballot(bd[r] <= ds));
-                    if (cnt < ef) accepted |= 1ull << sidx;
-                    else fbound = min(fbound, ds);
-                }
+                PIPE_CNT(7, __popcll(__ballot(have && od < B.fbound)));   // the prefilter's survivors
+                unsigned long long accepted;
+                B = beam_accept(B, have, od, (int)nnew, ef, accepted);
                 const int na = __popcll(accepted);
-                UP_T(t3);
-                UP_ACC(2, t3 - t2); UP_CNT(8, na); UP_CNT(9, na == 1 ? 1 : 0);
+                PIPE_T(t3);
+                PIPE_ACC(2, t3 - t2); PIPE_CNT(8, na); PIPE_CNT(9, na == 1 ? 1 : 0);
                 if (na) {
-                    if (n + na > (64 * NB)) {
-                        // ---- compaction (beam_compact): whatever lies beyond the bound `fbound` when that frees enough slots, else beyond
-                        // the exact ef-th smallest distance image of B
-                        const bool by_bound = beam_compact<NB>(bd, bi, cdv, n, fbound, ef, na, C, stage_flag, lane, lt_mask);
-                        UP_CNT(by_bound ? 10 : 11, 1);   // slot 10: by the bound, slot 11: by the exact select
+                    if (B.n + na > (64 * NB)) {
+                        bool by_bound;
+                        B = beam_compact(B, ef, na, C, stage_flag, lane, by_bound);
+                        PIPE_CNT(by_bound ? 10 : 11, 1);   // slot 10: by the bound, slot 11: by the exact select
                         nexp = 0;
 #pragma unroll
-                        for (int r = 0; r < NB; ++r) nexp += __popcll(__ballot(bd[r] != SLOT_EMPTY && cdv[r] == SLOT_EMPTY));
-                        if (n + na > (64 * NB)) { overflow = true; break; }
-                        ru_valid = beam_best_id(cdv, bi, ru_o, ru_id);  // may have been dropped
-                        if (ru_valid) rowr = load_row(ru_id);
-                        ru_closer = 0;
-                        if (nexp >= ef) {
-#pragma unroll
-                            for (int r = 0; r < NB; ++r) ru_closer += __popcll(__ballot(bd[r] < ru_o));
-                        }
+                        for (int r = 0; r < NB; ++r) nexp += __popcll(__ballot(B.bd[r] != SLOT_EMPTY && B.cdv[r] == SLOT_EMPTY));
+                        if (B.n + na > (64 * NB)) { overflow = true; break; }
+                        ru = beam_select(B);  // may have been dropped
+                        if (ru.have) rowr = load_row(ru.id);
+                        ru_closer = nexp >= ef ? beam_count_closer(B, ru.o) : 0;
                     }
-                    if (nexp >= ef) ru_closer += __popcll(accepted & __ballot(od < ru_o));
-                    // ---- one or two accepted neighbours (every step outside a layer's fill phase): each enters its slot n, n + 1 through two scalar
-                    // reads of its lane — no ds_permute round trip (the pair came back ~130 cycles later, and the NEXT step's selection reads the
-                    // beam first thing) and no 64-lane select tree; the same loop keeps the best accepted neighbour in pop order
-#ifndef MDB_HNSW_NO_FAST_PUSH
-                    if (na <= 2) {
-                        unsigned long long am2 = accepted;
-                        int pos = n;
-                        while (am2) {
-                            const int sidx = __ffsll((long long)am2) - 1;
-                            am2 &= am2 - 1;
-                            const uint32_t ao = (uint32_t)__builtin_amdgcn_readlane((int)od, sidx);
-                            const uint32_t ai = (uint32_t)__builtin_amdgcn_readlane((int)id, sidx);
-                            const bool me = lane == (pos & 63);
-                            const int rg = pos >> 6;   // wave-uniform
-#pragma unroll
-                            for (int r = 0; r < NB; ++r) {
-                                if (rg == r) {
-                                    bd[r] = me ? ao : bd[r];
-                                    bi[r] = me ? ai : bi[r];
-                                    cdv[r] = me ? ao : cdv[r];
-                                }
-                            }
-                            ++pos;
-                            if (!best_have || ao < best_o || (ao == best_o && ai > best_id)) { best_o = ao; best_id = ai; best_have = true; }
-                        }
-                    } else
-#endif
-                    {
-                        // ---- push all accepted neighbours: slots n .. n+na-1, in edge order (forward lane permute)
-                        {
-                            const bool mine = (accepted >> lane) & 1ull;
-                            const int dest = mine ? (n + __popcll(accepted & lt_mask)) & 63 : (n + na) & 63;
-                            const uint32_t rod = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)od);
-                            const uint32_t rid = (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)id);
-                            const int rel = (lane - n) & 63;
-                            const bool got = rel < na;
-                            const int reg = (n + rel) >> 6;
-    #pragma unroll
-                            for (int r = 0; r < NB; ++r) {
-                                const bool w = got && reg == r;
-                                bd[r] = w ? rod : bd[r];
-                                bi[r] = w ? rid : bi[r];
-                                cdv[r] = w ? rod : cdv[r];
-                            }
-                        }
-                        // best accepted neighbour in pop order (smallest distance, largest id)
-                        if (na > 2) {
-                            const bool mine = (accepted >> lane) & 1ull;
-                            best_o = wave_min_u32(mine ? od : SLOT_EMPTY);
-                            best_id = wave_max_u32(mine && od == best_o ? id : 0u);
-                            best_have = true;
-                        } else {
-                            unsigned long long am = accepted;
-                            while (am) {
-                                const int sidx = __ffsll((long long)am) - 1;
-                                am &= am - 1;
-                                const uint32_t ao = (uint32_t)__builtin_amdgcn_readlane((int)od, sidx);
-                                const uint32_t ai = (uint32_t)__builtin_amdgcn_readlane((int)id, sidx);
-                                if (!best_have || ao < best_o || (ao == best_o && ai > best_id)) { best_o = ao; best_id = ai; best_have = true; }
-                            }
-                        }
-                    }
-                    n += na;
+                    if (nexp >= ef) ru_closer += __popcll(accepted & __ballot(od < ru.o));   // this step's pushes
+                    B = beam_push(B, accepted, od, id, lane, best);
                 }
-                UP_T(t4);
-                UP_ACC(3, t4 - t3);
+                PIPE_T(t4);
+                PIPE_ACC(3, t4 - t3);
             }
-            UP_T(t5);
-            UP_T2(p0);   // (debug 2: every outstanding load — the runner-up's row — retired here)
-            UP_ACC2(8, p0 - t5);
-            // ---- candidates.pop(): runner-up vs best accepted; stop when it is farther than furthest
-            const bool take_ru = ru_valid && (!best_have || ru_o < best_o || (ru_o == best_o && ru_id > best_id));
-            if (!take_ru && !best_have) {
-                stop = true;  // no candidate left
+            PIPE_T(t5);
+            PIPE_T2(p0);   // (debug 2: every outstanding load — the runner-up's row — retired here)
+            PIPE_ACC2(8, p0 - t5);
+            // ---- candidates.pop()
+            BeamPop pop;
+            B = beam_pop(B, ru, nexp >= ef ? ru_closer : 0, best, nexp >= ef, ef, pop);
+            if (pop == BEAM_POP_STOP) {
+                stop = true;
             } else {
-                int closer = nexp >= ef ? ru_closer : 0;
-                if (!take_ru) {
-                    closer = 0;
-                    if (nexp >= ef) {
-#pragma unroll
-                        for (int r = 0; r < NB; ++r) closer += __popcll(__ballot(bd[r] < best_o));
-                    }
-                }
-                if (closer >= ef) {
-                    stop = true;  // `distance > furthest.distance` (index.rs:246-248)
-                } else if (take_ru) {
-#pragma unroll
-                    for (int r = 0; r < NB; ++r)
-                        if (bi[r] == ru_id) cdv[r] = SLOT_EMPTY;   // ids are unique in B
-                    rowv = rowr;
-                    ++nexp;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < NB; ++r)
-                        if (bi[r] == best_id) cdv[r] = SLOT_EMPTY;
-                    rowv = load_row(best_id);
-                    ++nexp;
-                }
+                rowv = pop == BEAM_POP_RUNNER_UP ? rowr : load_row(best.id);
+                ++nexp;
             }
-            UP_T(t6);
-            UP_ACC(4, t6 - t5);
-            UP_ACC2(9, t6 - p0);
+            PIPE_T(t6);
+            PIPE_ACC(4, t6 - t5);
+            PIPE_ACC2(9, t6 - p0);
         }
         if (overflow) break;
-        // ---- a layer hands its nearest point down (index.rs:177-181: smallest distance, then smallest id)
-        {
-            uint32_t m = bd[0];
-#pragma unroll
-            for (int r = 1; r < NB; ++r) m = min(m, bd[r]);
-            m = wave_min_u32(m);
-            uint32_t im = 0xFFFFFFFFu;
-#pragma unroll
-            for (int r = 0; r < NB; ++r) im = bd[r] == m ? min(im, bi[r]) : im;
-            ep = wave_min_u32(im);
-        }
+        // ---- a layer hands its nearest point down
+        ep = beam_nearest_id(B);
     }
     const bool nan_seen = __ballot(nan_lane) != 0;
     // the hand-over fields are re-read from the kernarg segment (HnswUpArgs is the first kernel argument of both kernels) behind an opaque
