@@ -169,6 +169,10 @@ mdb_status mdb_wait(mdb_ctx* ctx);
 int mdb_poll(mdb_ctx* ctx);
 const char* mdb_last_error(mdb_ctx* ctx);
 mdb_status mdb_get_stats(mdb_ctx* ctx, mdb_stats* out);
+/* diagnostics of the last mdb_hnsw_ann_search call on the context (waits for the stream): the number of its queries whose upper layers
+ * the frontier traversal (MDB_HNSW_CLOSURE) handed to the sequential kernels — exact distance ties at its stop test, or a NaN
+ * distance.  Rows, scores and mdb_stats do not depend on it. */
+mdb_status mdb_hnsw_closure_fallbacks(mdb_ctx* ctx, uint64_t* out);
 /* free / total bytes of the context's device after the stream has drained (hipMemGetInfo): the difference around a *_load /
  * *_create call is what that index keeps resident in HBM — tiles, codes, graphs AND the load-time accelerators (bf16 fragments,
  * row-major copies, sample stores), i.e. the multiplier over the file bytes.  No reference counterpart (the reference mmaps). */

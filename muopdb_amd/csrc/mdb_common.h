@@ -68,7 +68,8 @@
     X(hnsw_table64_min_b, "MDB_HNSW_TABLE64_MIN_B", 32) /* smallest batch that takes the lane = query table kernel */ \
     X(hnsw_no_wide, "MDB_HNSW_NO_WIDE", 0)             /* 256 < ef <= 448 through the general kernel instead of the 8-register beam */ \
     X(hnsw_rank, "MDB_HNSW_RANK", 2)                   /* upper layers on sorted positions (mdb_hnsw_rank.hip.h: bitmaps over rank instead of the register beam): bit 0 the layer-1 / single upper launch, bit 1 the split path's top launch */ \
-    X(hnsw_no_split, "MDB_HNSW_NO_SPLIT", 0)           /* upper layers: table pass, then ONE traversal launch (no top / layer-1 split) */ \
+    X(hnsw_closure, "MDB_HNSW_CLOSURE", 1)             /* upper layers of the table path frontier by frontier (mdb_hnsw_closure.hip.h), the sequential kernels behind MDB_HNSW_RANK only for the queries it flags; 0: the sequential kernels for every query */ \
+    X(hnsw_no_split, "MDB_HNSW_NO_SPLIT", 0)          /* upper layers: table pass, then ONE traversal launch (no top / layer-1 split) */ \
     X(hnsw_table_min_b, "MDB_HNSW_TABLE_MIN_B", 1)     /* smallest batch served by the table path */               \
     X(hnsw_nb4_slack, "MDB_HNSW_NB4_SLACK", 48)        /* table path: ef + this <= 256 runs the beam on FOUR registers of 64 slots (0: always five) */ \
     X(hnsw_dbg, "MDB_HNSW_DBG", 0)                                                                                  \
@@ -99,6 +100,9 @@
     X(pq3_blocks, "MDB_PQ3_BLOCKS", 512)                                                                            \
     X(pq3_cap, "MDB_PQ3_CAP", 2048)                                                                                 \
     X(pq3_block, "MDB_PQ3_BLOCK", 512)
+// d_counters word (among the words 4..15 that only MDB_PIPE_DBG builds use otherwise): queries of the last HNSW call whose upper
+// layers the frontier form handed to the sequential kernels (mdb_hnsw_closure_fallbacks)
+#define MDB_CTR_CLOSURE_FALLBACKS 4
 struct mdb_options {
 #define X(field, name, dflt) long long field = dflt;
     MDB_OPTIONS(X)

@@ -308,6 +308,15 @@ mdb_status mdb_get_stats(mdb_ctx* ctx, mdb_stats* out) {
     return MDB_OK;
 }
 
+mdb_status mdb_hnsw_closure_fallbacks(mdb_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return MDB_ERR_INVALID_ARG;
+    MDB_HIP(ctx, hipSetDevice(ctx->device));
+    MDB_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 256, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *out = ctx->dev_counters ? ctx->h_counters[MDB_CTR_CLOSURE_FALLBACKS] : 0;
+    return MDB_OK;
+}
+
 }  // extern "C"
 
 // ============================================================================================

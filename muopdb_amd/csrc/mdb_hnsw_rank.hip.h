@@ -756,13 +756,20 @@ __host__ __device__ inline size_t rk_lds_bytes(uint32_t vis_words, uint32_t nu_p
     return UP_LDS_VIS + (size_t)vis_words * 4 + (size_t)nu_pad * 4 + (size_t)RK_HIST_WORDS(nt) * 4 + 64 * 4 + (size_t)extra_words * 4;
 }
 
-// layers a.layer_hi .. a.layer_lo on the table rows of an earlier launch: sort the query's row, traverse
+// layers a.layer_hi .. a.layer_lo on the table rows of an earlier launch: sort the query's row, traverse — or, when the launch runs
+// the frontier form (a.fb_role CL_ROLE_BOTTOM / CL_ROLE_SINGLE), the block of mdb_hnsw_closure.hip.h, which wants these 1024 threads
 #define RK_BLOCK 1024
+template <int NT> __device__ void closure_bottom_block(const HnswUpArgs& a);
 template <int NW>
 __global__ __launch_bounds__(RK_BLOCK) void hnsw_upper_rank_kernel(HnswUpArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     uint32_t* const vis = (uint32_t*)(lds + UP_LDS_VIS);
     const int qi = blockIdx.x, lane = threadIdx.x & 63;
+    if (a.fb_role == CL_ROLE_BOTTOM || a.fb_role == CL_ROLE_SINGLE) {
+        closure_bottom_block<RK_BLOCK>(a);
+        return;
+    }
+    if (a.fb && !a.fb[qi]) return;   // the fallback launch behind the frontier form: only the flagged queries run
     uint16_t* const bufA = (uint16_t*)(vis + a.vis_words);
     uint16_t* const bufB = bufA + a.nu_pad;
     uint32_t* const hist = (uint32_t*)(bufB + a.nu_pad);

@@ -289,7 +289,21 @@ struct HnswUpArgs {
     const float* q;
     int qstride;
     int dbg_on;               // MDB_PIPE_DBG builds: this launch adds its cycle sums to counters[4..15] (MDB_HNSW_DBG bit 0: bottom launch, bit 1: top)
+    // frontier form (mdb_hnsw_closure.hip.h): fb[q] != 0 = the query's upper layers are re-run by the sequential kernels; fb_role: what
+    // this launch does with the word (CL_ROLE_*; nullptr / 0: no closure launch in this call)
+    uint32_t* fb;
+    int fb_role;
+    const uint32_t* top_map;  // a closure launch over every upper layer: the TOP set (layers >= 2) in this launch's numbering, for its own theta
+    uint32_t top_n;
+    int cl_tlds;              // closure launch behind the table: the query's row is copied into LDS
 };
+// roles of a launch in the fallback protocol (HnswUpArgs::fb_role)
+#define CL_ROLE_NONE 0
+#define CL_ROLE_TOP 1            // closure, the split path's top launch: fb[q] = flagged (the counter words are being cleared by this very launch)
+#define CL_ROLE_BOTTOM 2         // closure behind CL_ROLE_TOP: a query flagged above is skipped; fb[q] set and counted when flagged here or above
+#define CL_ROLE_SINGLE 3         // closure over every upper layer: fb[q] = flagged, counted
+#define CL_ROLE_FALLBACK 4       // the sequential kernels: blocks of unflagged queries exit at once
+
 
 #define UP_LDS_STAGE 0                 // 512 keys (compaction staging)
 #define UP_LDS_FLAG 4096               // 512 words
@@ -527,6 +541,7 @@ __global__ __launch_bounds__(UP_BLOCK) void hnsw_upper_kernel(HnswUpArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     uint32_t* const vis = (uint32_t*)(lds + UP_LDS_VIS);
     const int qi = blockIdx.x, lane = threadIdx.x & 63;
+    if (a.fb && !a.fb[qi]) return;   // the fallback launch behind the frontier form: only the flagged queries run
     const uint32_t* const tg = a.table + (size_t)qi * a.nu_pad;
     uint32_t* const tl = vis + a.vis_words;   // TLDS: the row's copy (vis_words is a multiple of 4: 16-byte aligned; nu_pad is a multiple of 64)
     for (uint32_t i = threadIdx.x; i < a.vis_words; i += UP_BLOCK) vis[i] = a.in_vis ? a.in_vis[(size_t)qi * a.vis_words + i] : 0u;
@@ -541,6 +556,38 @@ __global__ __launch_bounds__(UP_BLOCK) void hnsw_upper_kernel(HnswUpArgs a) {
 }
 
 #include "mdb_hnsw_rank.hip.h"
+#include "mdb_hnsw_closure.hip.h"
+
+// a top block of the split path's first launch in the frontier form (a.fb_role == CL_ROLE_TOP): it evaluates its query against the TOP
+// set itself, as the sequential forms do, and traverses the layers >= 2 with all four waves
+template <int METRIC, int N16>
+__device__ __forceinline__ void closure_top_block(const HnswUpArgs& a, char* lds) {
+    const ClLds L = cl_carve((uint32_t*)lds, a.vis_words, a.out_words);
+    const int qi = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t i = threadIdx.x; i < a.vis_words; i += 256) L.vis[i] = 0u;
+    // the block's own table row: one wave per tile of 64 points, thread = point (exact association, DPP-broadcast query chunks)
+    const float* const ql = a.q + (size_t)qi * a.qstride + (lane & 15);
+    for (uint32_t tile = wave; tile < a.self_ntiles; tile += 4) {
+        const float4* tp = a.self_tiles + (size_t)tile * (4 * N16) * MDB_TILE + lane;
+        float acc[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < N16; ++c) {
+            float4 x[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) x[t] = tp[(size_t)(4 * c + t) * MDB_TILE];
+            const float xv[16] = {x[0].x, x[0].y, x[0].z, x[0].w, x[1].x, x[1].y, x[1].z, x[1].w,
+                                  x[2].x, x[2].y, x[2].z, x[2].w, x[3].x, x[3].y, x[3].z, x[3].w};
+            t16_accumulate<METRIC>(acc, ql[16 * c], xv);
+        }
+        const uint32_t v = tile * MDB_TILE + lane;
+        L.row[v] = v < a.nu ? f32_orderable(finish_distance<METRIC>(__fadd_rn(0.0f, reduce_ordered<16>(acc)))) : SLOT_EMPTY;
+    }
+    __syncthreads();
+    closure_traverse<256>(a, qi, L, L.row);
+}
+
 
 // The split path (batches of >= 32 queries, d = 16 n16 <= 128): ONE launch whose first b blocks traverse the layers >= 2 — ~1 k points:
 // each block evaluates its query against them itself (the thread = point arithmetic of hnsw_upper_table16_kernel, the row goes
@@ -598,6 +645,10 @@ __global__ __launch_bounds__(256, 2) void hnsw_upper_top_rank_kernel(HnswUpArgs 
         return;
     }
     if (zero16 && blockIdx.x == 0 && threadIdx.x < 16) zero16[threadIdx.x] = 0ull;
+    if (a.fb_role == CL_ROLE_TOP) {   // the frontier form (mdb_hnsw_closure.hip.h) is a mode of this launch
+        closure_top_block<METRIC, N16>(a, lds);
+        return;
+    }
     uint32_t* const vis = (uint32_t*)(lds + UP_LDS_VIS);
     const int qi = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* const tl = vis + a.vis_words;
@@ -637,9 +688,12 @@ __global__ __launch_bounds__(256, 2) void hnsw_upper_top_rank_kernel(HnswUpArgs 
 }
 
 // launch of hnsw_upper_kernel over layers layer_hi .. 1 (the last launch before layer 0: out_ep holds point ids, the bitmap as is)
+// fb: this is the fallback launch behind the frontier form — only the queries it flagged run
 static mdb_status upper_launch_bottom(mdb_ctx* ctx, const HnswUpper& up, const uint32_t* d_table, size_t b, uint32_t ef, const HnswUpperOut& out,
-                                      int layer_hi, const uint32_t* in_ep, const uint32_t* in_ovf, const uint32_t* in_vis, const uint32_t* in_cnt) {
+                                      int layer_hi, const uint32_t* in_ep, const uint32_t* in_ovf, const uint32_t* in_vis, const uint32_t* in_cnt,
+                                      uint32_t* fb = nullptr) {
     HnswUpArgs a{};
+    a.fb = fb; a.fb_role = fb ? CL_ROLE_FALLBACK : CL_ROLE_NONE;
     a.rows = up.rows.p; a.table = d_table; a.row_layer0 = 1;
     a.nu = up.nu; a.nu_pad = (uint32_t)up.tiles.ntiles * MDB_TILE; a.su = up.su; a.small_layer = up.small_layer;
     a.entry_c = up.entry_c;
@@ -683,7 +737,66 @@ mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const D
     const uint32_t nu_pad = (uint32_t)up.tiles.ntiles * MDB_TILE;
     const uint32_t nu2_pad = (uint32_t)up.tiles2.ntiles * MDB_TILE;
     const uint32_t words2 = (up.nu2 / 32 + 4) & ~3u;
-    const size_t lds_top = UP_LDS_VIS + (size_t)words2 * 4 + (size_t)nu2_pad * 4 + (size_t)out.words * 4;
+    // ---- the frontier form (mdb_hnsw_closure.hip.h): table + top layers, layer 1, then the fallback launch for the flagged queries
+    if (ctx->opt.hnsw_closure && up.su <= 64 && up.layers >= 1) {
+        const size_t lds_lim = 160 * 1024 - 512;
+        const size_t lds_row = cl_lds_words(out.words, 0, nu_pad) * 4, lds_norow = cl_lds_words(out.words, 0, 0) * 4;
+        const bool tlds = lds_row <= lds_lim && !ctx->opt.hnsw_table_no_lds;
+        const size_t lds_ctop = cl_lds_words(words2, out.words, nu2_pad) * 4;
+        const bool csplit = up.nu2 > 0 && up.layers >= 2 && up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 &&
+                            (long long)b >= ctx->opt.hnsw_table64_min_b && !ctx->opt.hnsw_no_split &&
+                            lds_ctop <= 80 * 1024 - 512;   // (two blocks per CU: the table blocks of the same launch share it)
+        if (lds_norow <= lds_lim) {
+            uint32_t* const st_ep = d_state;
+            uint32_t* const st_ovf = st_ep + b;
+            uint32_t* const st_cnt = st_ovf + b;
+            uint32_t* const st_vis = st_cnt + 4 * b;
+            uint32_t* const fb = st_vis + (size_t)b * out.words;   // [b] behind the hand-over state (d_state holds b * (words + 8) + 64 words)
+            HnswUpArgs c{};
+            c.rows = up.rows.p; c.table = d_table; c.row_layer0 = 1;
+            c.nu = up.nu; c.nu_pad = nu_pad; c.su = up.su; c.small_layer = up.small_layer; c.entry_c = up.entry_c;
+            c.layer_hi = (int)up.layers; c.layer_lo = 1;
+            c.ef = (int)ef;
+            c.vis_words = out.words;
+            c.ep_map = up.ids.p; c.vis_map = nullptr; c.out_words = out.words;
+            c.out_ep = out.ep; c.out_ovf = out.ovf; c.out_vis = out.vis; c.out_cnt = out.cnt;
+            c.flags = ctx->d_flags; c.counters = ctx->d_counters;
+            c.fb = fb; c.fb_role = CL_ROLE_SINGLE;
+            if (up.nu2 > 0 && up.map21.p) { c.top_map = up.map21.p; c.top_n = up.nu2; }
+            if (csplit) {
+                HnswUpArgs t{};
+                t.rows = up.rows2.p; t.table = nullptr; t.row_layer0 = 2;
+                t.nu = up.nu2; t.nu_pad = nu2_pad; t.su = up.su; t.small_layer = up.small_layer; t.entry_c = up.entry_c2;
+                t.layer_hi = (int)up.layers; t.layer_lo = 2;
+                t.ef = (int)ef;
+                t.vis_words = words2;
+                t.ep_map = up.map21.p; t.vis_map = up.map21.p; t.out_words = out.words;
+                t.out_ep = st_ep; t.out_ovf = st_ovf; t.out_vis = st_vis; t.out_cnt = st_cnt;
+                t.flags = ctx->d_flags; t.counters = ctx->d_counters;
+                t.self_tiles = (const float4*)up.tiles2.data.p; t.self_ntiles = (uint32_t)up.tiles2.ntiles; t.n16 = p.n16; t.q = d_q; t.qstride = qstride;
+                t.fb = fb; t.fb_role = CL_ROLE_TOP;
+                const unsigned tgx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), tgy = (unsigned)((b + 63) / 64);
+                MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
+                    return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
+                        return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), 1>, dim3((unsigned)b + tgx * tgy), 256, lds_ctop, t, (uint32_t)b,
+                                          up.rows_nat.p, up.nu, d_table, nu_pad, tgx, zero16);
+                    });
+                }));
+                MDB_HIP(ctx, hipGetLastError());
+                c.layer_hi = 1;
+                c.in_ep = st_ep; c.in_ovf = st_ovf; c.in_vis = st_vis; c.in_cnt = st_cnt;
+                c.fb_role = CL_ROLE_BOTTOM;
+            } else {
+                MDB_TRY(hnsw_upper_table(ctx, up, metric, p, d_q, qstride, b, d_table, zero16));
+            }
+            c.cl_tlds = tlds ? 1 : 0;
+            MDB_TRY(mdb_launch(ctx, hnsw_upper_rank_kernel<1>, dim3((unsigned)b), RK_BLOCK, tlds ? lds_row : lds_norow, c));
+            MDB_HIP(ctx, hipGetLastError());
+            // the sequential traversal of every upper layer for the flagged queries (one launch, table rows of the launches above)
+            return upper_launch_bottom(ctx, up, d_table, b, ef, out, (int)up.layers, nullptr, nullptr, nullptr, nullptr, fb);
+        }
+    }
+    const size_t lds_top =UP_LDS_VIS + (size_t)words2 * 4 + (size_t)nu2_pad * 4 + (size_t)out.words * 4;
     const bool split = up.nu2 > 0 && up.layers >= 2 && up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 &&
                        (long long)b >= ctx->opt.hnsw_table64_min_b && !ctx->opt.hnsw_no_split && lds_top <= 160 * 1024 - 512 && ef <= 256;
     // the top blocks on sorted positions: their LDS holds the row, its two rank tables and the sort's histograms

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "mdb_multi_spann_search_filtered", "mdb_multi_spann_attach", "mdb_multi_spann_search_submit",
     "mdb_set_option", "mdb_get_option", "mdb_points_block_bytes", "mdb_points_block_views", "mdb_ivf_search_shard", "mdb_ivf_merge_shards",
     "mdb_spann_search_shard", "mdb_spann_merge_shards", "mdb_multi_spann_search_shard", "mdb_multi_spann_merge_shards", "mdb_spann_probe_row_words", "mdb_multi_spann_probes", "mdb_multi_spann_search_shard_probes",
-    "mdb_allgather_blocks", "mdb_device_mem_info",
+    "mdb_allgather_blocks", "mdb_device_mem_info", "mdb_hnsw_closure_fallbacks",
 ]
 
 
@@ -188,6 +188,12 @@ class Context:
         s = Stats()
         self.check(self.lib.mdb_get_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in Stats._fields_}
+
+    def closure_fallbacks(self):
+        """queries of the last HNSW search whose upper layers the frontier form handed to the sequential kernels; synchronises."""
+        v = C.c_uint64()
+        self.check(self.lib.mdb_hnsw_closure_fallbacks(self.h, C.byref(v)))
+        return v.value
 
     def set_profiling(self, on):
         # True -> 3 (every bracketed kernel); 1 = scan kernels only, 2 = HNSW traversal only
