@@ -20,9 +20,21 @@
 // hnsw_upper_kernel's closure of a layer of <= 64 points is the special case theta = +inf.
 // What the counts cannot decide is an uncertain u that passes the strict test while ef OTHER evaluated points are no farther: whether
 // the reference ever accepted u depends on the discovery order.  That, and any evaluated NaN (whose flag the sequential kernels raise
-// where the reference panics), makes the query a FALLBACK: the block publishes nothing (its visited set is a copy in LDS), sets
-// fb[q], and the sequential traversal re-runs the query's upper layers in a follow-up launch whose blocks exit at once unless their
-// query is flagged (tests/closure_model.py restates both forms; tests/test_gpu_hnsw_closure.py).
+// where the reference panics), makes the query a FALLBACK: the block publishes nothing (its visited set is a copy in LDS) and the
+// sequential traversal re-runs what the block ran, no more (tests/closure_model.py restates both forms; tests/test_gpu_hnsw_closure.py,
+// test_gpu_hnsw_closure_local.py):
+//   * a TOP block of the split path (CL_ROLE_TOP_LOCAL) re-runs its layers >= 2 itself, on sorted positions: the row is carried over
+//     to the layout of mdb_hnsw_rank.hip.h, rank_tables + upper_traverse_rank1 publish the hand-over the sequential top launch has
+//     always given layer 1 (NaN word included), and fb[q] = CL_FB_COUNT asks the layer-1 launch to count the query — the top launch
+//     is the one that clears the counter words.  The layer-1 launch then runs the query like any other;
+//   * a query flagged on layer 1 (or handed a NaN word or an overflow flag from above) sets fb[q] = CL_FB_RERUN, and a follow-up
+//     launch of the sequential kernels, whose blocks exit at once unless their query's word says so, re-runs LAYER 1 from the top
+//     launch's hand-over, which is still intact;
+//   * where the top block cannot hold the sorted-position layout (more than 2048 TOP points, MDB_HNSW_RANK bit 1 clear) and in a
+//     launch over every upper layer (CL_ROLE_SINGLE: batches below the split path) the protocol is the first one built: fb[q] =
+//     CL_FB_RERUN from whichever launch flags, a query flagged above is skipped on layer 1, the follow-up launch starts at the top.
+// mdb_hnsw_closure_fallbacks counts a query once, wherever it was flagged; every call writes fb[q] of each of its queries before it
+// reads it (the words live in scratch that is reused).
 // The form adds no kernel of its own: it is a mode of the launches it replaces — the 1024-thread hnsw_upper_rank_kernel behind the table
 // (one block per CU either way: its LDS holds the query's table row) and the top blocks of hnsw_upper_top_rank_kernel — chosen by
 // HnswUpArgs::fb_role, so the launch shape, the table blocks and the kernel inventory stay what they were.
@@ -43,6 +55,7 @@
 #define CL_SH_KMAX 10
 #define CL_SH_MINU 12            // u64: min (image, ~id) over evaluated and unexpanded
 #define CL_SH_MINE 14            // u64: min (image, id) over evaluated
+#define CL_SH_FLAGGED 16         // how closure_traverse ended, for its caller
 #define CL_SH_WORDS 32
 struct ClLds {
     uint32_t *sh, *hist, *fr, *vis, *ev, *ex, *vis_out, *row;
@@ -145,9 +158,10 @@ __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, 
 
 // Layers a.layer_hi .. a.layer_lo of query qi on the table row `tq` (LDS or global memory), by every thread of the block.  L.vis holds
 // the visited set handed in, and the caller's barrier stands behind it and the row.  Publishes the hand-over exactly as
-// upper_traverse_wave0 leaves it, or — flagged — only fb[q].
+// upper_traverse_wave0 leaves it, or — flagged — only fb[q] (CL_ROLE_TOP_LOCAL: nothing at all; the caller resolves the flag).
+// Returns the flag, the same for every thread: read back from an LDS word, so that the compiler knows it.
 template <int NT>
-__device__ __forceinline__ void closure_traverse(const HnswUpArgs& a, const int qi, const ClLds& L, const uint32_t* __restrict__ tq) {
+__device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int qi, const ClLds& L, const uint32_t* __restrict__ tq) {
     const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t ef = (uint32_t)a.ef, su = a.su;
     uint32_t gs = 1;                                   // lanes per frontier point: the row stride rounded up to a power of two (<= 64)
@@ -161,7 +175,7 @@ __device__ __forceinline__ void closure_traverse(const HnswUpArgs& a, const int 
     const uint32_t theta_top = (a.top_map && a.layer_hi >= 2) ? cl_theta<NT>(tq, a.top_map, a.top_n, ef, L.hist, L.sh) : theta;
     uint32_t ep = a.in_ep ? a.in_ep[qi] : a.entry_c;
     uint32_t evals = a.in_cnt ? a.in_cnt[4 * qi + 0] : 0u, expanded = a.in_cnt ? a.in_cnt[4 * qi + 1] : 0u;
-    bool flagged = (a.in_cnt && a.in_cnt[4 * qi + 2]) || ep >= a.nu;
+    bool flagged = (a.in_cnt && a.in_cnt[4 * qi + 2]) || (a.in_ovf && a.in_ovf[qi] != 0u) || ep >= a.nu;
     uint32_t* cur = L.fr;
     uint32_t* nxt = L.fr + CL_FR_CAP;
 
@@ -282,13 +296,16 @@ __device__ __forceinline__ void closure_traverse(const HnswUpArgs& a, const int 
         expanded += L.sh[CL_SH_EXPANDED];
     }
     __syncthreads();
-    const bool count = a.fb_role == CL_ROLE_BOTTOM || a.fb_role == CL_ROLE_SINGLE;
-    if (flagged) {
-        if (tid == 0) {
-            a.fb[qi] = 1u;
-            if (count) atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
+    if (tid == 0) L.sh[CL_SH_FLAGGED] = flagged ? 1u : 0u;
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane((int)L.sh[CL_SH_FLAGGED]) != 0) {
+        if (tid == 0 && a.fb_role != CL_ROLE_TOP_LOCAL) {
+            // (a query the top launch resolved itself was counted at this block's entry: once, wherever it was flagged)
+            const bool counted = a.fb_role == CL_ROLE_TOP || (a.fb_role == CL_ROLE_BOTTOM && a.fb[qi] == CL_FB_COUNT);
+            a.fb[qi] = CL_FB_RERUN;
+            if (!counted) atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
         }
-        return;
+        return true;
     }
     // ---- the hand-over (see upper_traverse_wave0)
     if (a.vis_map) {
@@ -310,7 +327,7 @@ __device__ __forceinline__ void closure_traverse(const HnswUpArgs& a, const int 
         for (uint32_t i = tid; i < a.vis_words; i += NT) a.out_vis[(size_t)qi * a.vis_words + i] = L.vis[i];
     }
     if (tid == 0) {
-        if (a.fb_role != CL_ROLE_BOTTOM) a.fb[qi] = 0u;   // (behind the top launch the word is already zero)
+        a.fb[qi] = CL_FB_CLEAN;                    // (behind the top launch the word may hold CL_FB_COUNT)
         a.out_ep[qi] = a.ep_map[ep];
         a.out_ovf[qi] = 0u;
         if (a.out_cnt) {
@@ -320,6 +337,7 @@ __device__ __forceinline__ void closure_traverse(const HnswUpArgs& a, const int 
             atomicAdd(&a.counters[1], (unsigned long long)expanded);
         }
     }
+    return false;
 }
 
 // layers a.layer_hi .. a.layer_lo on the table rows of an earlier launch: the body of hnsw_upper_rank_kernel's block when the launch
@@ -329,12 +347,15 @@ template <int NT>
 __device__ void closure_bottom_block(const HnswUpArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int qi = blockIdx.x;
-    if (a.fb_role == CL_ROLE_BOTTOM && (a.fb[qi] != 0u || (a.in_ovf && a.in_ovf[qi] != 0u))) {   // flagged above: the fallback launch takes it from the top
-        if (threadIdx.x == 0) {
-            a.fb[qi] = 1u;
-            atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
+    if (a.fb_role == CL_ROLE_BOTTOM) {
+        const uint32_t above = a.fb[qi];
+        if (above == CL_FB_RERUN) {                    // flagged above and left there: the follow-up launch takes it from the top
+            if (threadIdx.x == 0) atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
+            return;
         }
-        return;
+        // flagged above and resolved there (the hand-over is the sequential form's): counted here, where the counter words are no
+        // longer being cleared, and run like any other — thread 0 alone reads the word again should this pass flag it too
+        if (above == CL_FB_COUNT && threadIdx.x == 0) atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
     }
     const ClLds L = cl_carve((uint32_t*)lds, a.vis_words, a.vis_map ? a.out_words : 0u);
     const uint32_t* const tg = a.table + (size_t)qi * a.nu_pad;

@@ -289,8 +289,8 @@ struct HnswUpArgs {
     const float* q;
     int qstride;
     int dbg_on;               // MDB_PIPE_DBG builds: this launch adds its cycle sums to counters[4..15] (MDB_HNSW_DBG bit 0: bottom launch, bit 1: top)
-    // frontier form (mdb_hnsw_closure.hip.h): fb[q] != 0 = the query's upper layers are re-run by the sequential kernels; fb_role: what
-    // this launch does with the word (CL_ROLE_*; nullptr / 0: no closure launch in this call)
+    // frontier form (mdb_hnsw_closure.hip.h): fb[q] (CL_FB_*) = what is left to do for a query the form flagged; fb_role: what this
+    // launch does with the word (CL_ROLE_*; nullptr / 0: no closure launch in this call)
     uint32_t* fb;
     int fb_role;
     const uint32_t* top_map;  // a closure launch over every upper layer: the TOP set (layers >= 2) in this launch's numbering, for its own theta
@@ -300,9 +300,15 @@ struct HnswUpArgs {
 // roles of a launch in the fallback protocol (HnswUpArgs::fb_role)
 #define CL_ROLE_NONE 0
 #define CL_ROLE_TOP 1            // closure, the split path's top launch: fb[q] = flagged (the counter words are being cleared by this very launch)
-#define CL_ROLE_BOTTOM 2         // closure behind CL_ROLE_TOP: a query flagged above is skipped; fb[q] set and counted when flagged here or above
+#define CL_ROLE_BOTTOM 2         // closure behind CL_ROLE_TOP / _TOP_LOCAL: a query left flagged above is skipped; counted when flagged here or above
 #define CL_ROLE_SINGLE 3         // closure over every upper layer: fb[q] = flagged, counted
 #define CL_ROLE_FALLBACK 4       // the sequential kernels: blocks of unflagged queries exit at once
+#define CL_ROLE_TOP_LOCAL 5      // CL_ROLE_TOP whose block re-runs a flagged query itself, on sorted positions: every query is handed over,
+                                 // fb[q] = CL_FB_COUNT marks the flagged ones for the launch below to count
+// values of fb[q]; every call writes the word of each of its queries before it reads it (the scratch is reused from call to call)
+#define CL_FB_CLEAN 0u
+#define CL_FB_RERUN 1u           // the follow-up launch re-runs the query: from the top, or layer 1 alone behind CL_ROLE_TOP_LOCAL
+#define CL_FB_COUNT 2u           // flagged in the top launch and resolved there: not yet counted
 
 
 #define UP_LDS_STAGE 0                 // 512 keys (compaction staging)
@@ -558,10 +564,11 @@ __global__ __launch_bounds__(UP_BLOCK) void hnsw_upper_kernel(HnswUpArgs a) {
 #include "mdb_hnsw_rank.hip.h"
 #include "mdb_hnsw_closure.hip.h"
 
-// a top block of the split path's first launch in the frontier form (a.fb_role == CL_ROLE_TOP): it evaluates its query against the TOP
-// set itself, as the sequential forms do, and traverses the layers >= 2 with all four waves
+// a top block of the split path's first launch in the frontier form (a.fb_role CL_ROLE_TOP / CL_ROLE_TOP_LOCAL): it evaluates its query against the TOP
+// set itself, as the sequential forms do, and traverses the layers >= 2 with all four waves.  Returns closure_traverse's flag; the row
+// is still at `row` when it does.
 template <int METRIC, int N16>
-__device__ __forceinline__ void closure_top_block(const HnswUpArgs& a, char* lds) {
+__device__ __forceinline__ bool closure_top_block(const HnswUpArgs& a, char* lds, const uint32_t*& row) {
     const ClLds L = cl_carve((uint32_t*)lds, a.vis_words, a.out_words);
     const int qi = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint32_t i = threadIdx.x; i < a.vis_words; i += 256) L.vis[i] = 0u;
@@ -585,7 +592,8 @@ __device__ __forceinline__ void closure_top_block(const HnswUpArgs& a, char* lds
         L.row[v] = v < a.nu ? f32_orderable(finish_distance<METRIC>(__fadd_rn(0.0f, reduce_ordered<16>(acc)))) : SLOT_EMPTY;
     }
     __syncthreads();
-    closure_traverse<256>(a, qi, L, L.row);
+    row = L.row;
+    return closure_traverse<256>(a, qi, L, L.row);
 }
 
 
@@ -645,10 +653,6 @@ __global__ __launch_bounds__(256, 2) void hnsw_upper_top_rank_kernel(HnswUpArgs 
         return;
     }
     if (zero16 && blockIdx.x == 0 && threadIdx.x < 16) zero16[threadIdx.x] = 0ull;
-    if (a.fb_role == CL_ROLE_TOP) {   // the frontier form (mdb_hnsw_closure.hip.h) is a mode of this launch
-        closure_top_block<METRIC, N16>(a, lds);
-        return;
-    }
     uint32_t* const vis = (uint32_t*)(lds + UP_LDS_VIS);
     const int qi = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t* const tl = vis + a.vis_words;
@@ -657,10 +661,33 @@ __global__ __launch_bounds__(256, 2) void hnsw_upper_top_rank_kernel(HnswUpArgs 
     uint32_t* const hist = (uint32_t*)(bufB + a.nu_pad);
     uint32_t* const red = hist + RK_HIST_WORDS(256);
     uint32_t* const vis_out = red + 64;
+    const bool closure = a.fb_role == CL_ROLE_TOP || a.fb_role == CL_ROLE_TOP_LOCAL;
+    if (closure) {   // the frontier form (mdb_hnsw_closure.hip.h) is a mode of this launch
+        const uint32_t* row;
+        const bool flagged = closure_top_block<METRIC, N16>(a, lds, row);
+        if (NW != 1 || a.fb_role != CL_ROLE_TOP_LOCAL || !flagged) return;
+        // flagged (an exact tie at the stop test, a NaN): nothing was published and the closure's LDS is dead.  The block re-runs the
+        // query on sorted positions right here, as below; all that moves is the row (the layouts overlap: through registers,
+        // nu_pad <= 2048 = 8 words per thread)
+        uint32_t keep[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t i = threadIdx.x + 256u * j;
+            keep[j] = i < a.nu_pad ? row[i] : 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t i = threadIdx.x + 256u * j;
+            if (i < a.nu_pad) tl[i] = keep[j];
+        }
+        if (threadIdx.x == 0) a.fb[qi] = CL_FB_COUNT;
+    }
     for (uint32_t i = threadIdx.x; i < a.vis_words; i += UP_BLOCK) vis[i] = 0u;
     // the block's own table row: one wave per tile of 64 points, thread = point (exact association, DPP-broadcast query chunks)
     const float* const ql = a.q + (size_t)qi * a.qstride + (lane & 15);
-    for (uint32_t tile = wave; tile < a.self_ntiles; tile += UP_BLOCK / 64) {
+    // (behind the frontier form the row is already there: no tile is left to do)
+    for (uint32_t tile = closure ? a.self_ntiles : wave; tile < a.self_ntiles; tile += UP_BLOCK / 64) {
         const float4* tp = a.self_tiles + (size_t)tile * (4 * N16) * MDB_TILE + lane;
         float acc[16];
 #pragma unroll
@@ -763,6 +790,10 @@ mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const D
             c.flags = ctx->d_flags; c.counters = ctx->d_counters;
             c.fb = fb; c.fb_role = CL_ROLE_SINGLE;
             if (up.nu2 > 0 && up.map21.p) { c.top_map = up.map21.p; c.top_n = up.nu2; }
+            // a top block re-runs its flagged query itself, on sorted positions (upper_traverse_rank1: <= 2048 ranks), when its LDS
+            // holds that layout as well; the follow-up launch then has layer 1 alone to re-run, from the top launch's hand-over
+            const size_t lds_top_rank = rk_lds_bytes(words2, nu2_pad, 256, nu2_pad + out.words);
+            const bool local = csplit && (ctx->opt.hnsw_rank & 2) && nu2_pad <= 2048 && lds_top_rank <= 80 * 1024 - 512;
             if (csplit) {
                 HnswUpArgs t{};
                 t.rows = up.rows2.p; t.table = nullptr; t.row_layer0 = 2;
@@ -774,11 +805,12 @@ mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const D
                 t.out_ep = st_ep; t.out_ovf = st_ovf; t.out_vis = st_vis; t.out_cnt = st_cnt;
                 t.flags = ctx->d_flags; t.counters = ctx->d_counters;
                 t.self_tiles = (const float4*)up.tiles2.data.p; t.self_ntiles = (uint32_t)up.tiles2.ntiles; t.n16 = p.n16; t.q = d_q; t.qstride = qstride;
-                t.fb = fb; t.fb_role = CL_ROLE_TOP;
+                t.fb = fb; t.fb_role = local ? CL_ROLE_TOP_LOCAL : CL_ROLE_TOP;
                 const unsigned tgx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), tgy = (unsigned)((b + 63) / 64);
                 MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
                     return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
-                        return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), 1>, dim3((unsigned)b + tgx * tgy), 256, lds_ctop, t, (uint32_t)b,
+                        return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), 1>, dim3((unsigned)b + tgx * tgy), 256,
+                                          local && lds_top_rank > lds_ctop ? lds_top_rank : lds_ctop, t, (uint32_t)b,
                                           up.rows_nat.p, up.nu, d_table, nu_pad, tgx, zero16);
                     });
                 }));
@@ -792,7 +824,9 @@ mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const D
             c.cl_tlds = tlds ? 1 : 0;
             MDB_TRY(mdb_launch(ctx, hnsw_upper_rank_kernel<1>, dim3((unsigned)b), RK_BLOCK, tlds ? lds_row : lds_norow, c));
             MDB_HIP(ctx, hipGetLastError());
-            // the sequential traversal of every upper layer for the flagged queries (one launch, table rows of the launches above)
+            // the sequential traversal for the flagged queries (one launch, table rows of the launches above): of layer 1 alone, from the
+            // top launch's hand-over, when the top blocks resolve their own flags — of every upper layer otherwise
+            if (local) return upper_launch_bottom(ctx, up, d_table, b, ef, out, 1, st_ep, st_ovf, st_vis, st_cnt, fb);
             return upper_launch_bottom(ctx, up, d_table, b, ef, out, (int)up.layers, nullptr, nullptr, nullptr, nullptr, fb);
         }
     }
