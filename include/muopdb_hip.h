@@ -390,6 +390,33 @@ void mdb_multi_spann_free(mdb_multi_spann* ms);
  * users (call with users_out == NULL to size the array).  MDB_ERR_FORMAT if the bytes are not such a table. */
 mdb_status mdb_odht_user_table(const void* odht_bytes, size_t len, mdb_user_index_info* users_out, size_t cap, size_t* n_out);
 size_t mdb_multi_spann_num_users(const mdb_multi_spann* ms);
+
+/* ---------------------------------------------------------------- file checkers
+ * The HOST half of each *_load — everything it decides from the files' bytes before its first device call: headers, section bounds,
+ * every count, offset, point id and edge, the quantizer descriptor against the headers — run alone.  Host-only, no device needed
+ * and no context: the arguments are those of the matching *_load without `ctx` and `out`, plus `why` (may be NULL), which receives
+ * the refusal's message (what mdb_last_error would hold after the load), NUL-terminated and cut to why_cap bytes; "" on MDB_OK.
+ * The loaders call the same function first and upload what it produced, so the statuses are the loaders': MDB_OK means *_load will
+ * not refuse these bytes (it can still fail with MDB_ERR_OOM / MDB_ERR_HIP), and MDB_ERR_FORMAT / MDB_ERR_UNSUPPORTED (limits
+ * table above) / MDB_ERR_INVALID_ARG (descriptor, shard arguments) are returned before anything is sized from a file field.
+ * What they do NOT look at: the payload of an Elias-Fano list (only its header is checked here; a decoded id >= num_vectors is
+ * caught on the device, at load, as MDB_ERR_FORMAT).  tests/file_mutations.py holds a malformed file for every refusal.
+ * Multi-user collections: a user's blobs are located by the `*_offset` fields alone.  The `*_len` fields are NOT consulted, as in
+ * the reference (MultiSpannIndex::get_or_create_index passes only the four offsets to SpannReader::new_with_offsets,
+ * rs/index/src/multi_spann/index.rs:110-116): each blob is bounded by the shared file's end and by its own header's lengths. */
+mdb_status mdb_hnsw_check_files(const void* index_bytes, size_t index_len, size_t index_offset, const void* vectors_bytes,
+                                size_t vectors_len, size_t vectors_offset, const mdb_quant_desc* quant, char* why, size_t why_cap);
+mdb_status mdb_ivf_check_files(const void* index_bytes, size_t index_len, size_t index_offset, const void* vectors_bytes,
+                               size_t vectors_len, size_t vectors_offset, const mdb_quant_desc* quant, uint32_t shard_rank,
+                               uint32_t shard_world, char* why, size_t why_cap);
+mdb_status mdb_spann_check_files(const void* hnsw_index, size_t hnsw_index_len, size_t hnsw_index_offset, const void* hnsw_vectors,
+                                 size_t hnsw_vectors_len, size_t hnsw_vectors_offset, const void* ivf_index, size_t ivf_index_len,
+                                 size_t ivf_index_offset, const void* ivf_vectors, size_t ivf_vectors_len, size_t ivf_vectors_offset,
+                                 const mdb_quant_desc* quant, char* why, size_t why_cap);
+mdb_status mdb_multi_spann_check_files(const mdb_user_index_info* users, size_t n_users, uint32_t num_features, const void* hnsw_index,
+                                       size_t hnsw_index_len, const void* hnsw_vectors, size_t hnsw_vectors_len, const void* ivf_index,
+                                       size_t ivf_index_len, const void* ivf_vectors, size_t ivf_vectors_len, const mdb_quant_desc* quant,
+                                       uint32_t shard_rank, uint32_t shard_world, char* why, size_t why_cap);
 /* search_for_user :282-293 for a batch of (user_ids[i], queries[i]) pairs; unknown user =>
  * found_out[i] = 0 (`Err(_) => None`) */
 mdb_status mdb_multi_spann_search(mdb_multi_spann* ms, const mdb_u128* user_ids, const float* queries, size_t b,

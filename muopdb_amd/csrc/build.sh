@@ -27,6 +27,15 @@ for s in $SRCS; do
   fi
   objs="$objs $o"
 done
+# the loaders' host halves (mdb_files.cpp): plain C++, no HIP header — the same file tests/host/check_files_main.cpp builds with the sanitizers
+o=build/mdb_files.o
+if [ ! -f "$o" ] || [ mdb_files.cpp -nt "$o" ] || [ mdb_files.h -nt "$o" ] || [ ../../include/muopdb_hip.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
+  echo "g++ mdb_files.cpp"
+  rm -f "$o"
+  g++ -std=c++17 -O2 -fPIC -Wall -c mdb_files.cpp -o "$o" &
+  pids="$pids $!"
+fi
+objs="$objs $o"
 for p in $pids; do wait "$p" || { echo "build.sh: a translation unit failed to compile" >&2; exit 1; }; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs
 echo "built $OUT"

@@ -13,10 +13,9 @@
 
 #include "../../include/muopdb_hip.h"
 #include "mdb_arena.h"
+#include "mdb_files.h"   // MDB_TILE / MDB_UNIT, the byte readers, ef_header_error and the loaders' host halves
 
 #define MDB_WAVE 64
-#define MDB_TILE 64          // vectors per tile of the list-contiguous SoA layout (one per lane)
-#define MDB_UNIT 16          // f32 posting lists: slots per unit (a tile = four units 64 wide; a list's tail tile is 1-3 units, 16-48 wide: mdb_ivf.hip)
 #define MDB_BLOCK 256        // threads per scan block (4 tiles per round)
 #define MDB_KEY_MAX 0xFFFFFFFFFFFFFFFFull
 #define MDB_MAX_K 2048       // largest top-k / ef served by the on-chip selectors
@@ -319,24 +318,3 @@ struct PqDev {
     DevBuf<float> sdc;                 // [m][K][K] (optional, ivf_sdc_build): row sums of code a against code c per subspace
     std::vector<float> h_codebook;
 };
-
-// host-side byte readers (little-endian files)
-static inline uint32_t rd_u32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-static inline uint64_t rd_u64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }
-// overflow-checked a + b <= limit
-static inline bool fits(uint64_t a, uint64_t b, uint64_t limit) { return a <= limit && b <= limit - a; }
-// Host-side validation of one serialized Elias-Fano list (ef.rs:197-215 header: n, L, lower_words, upper_words) of `avail`
-// bytes BEFORE the device decoder trusts it: a corrupt header would otherwise make ef_low_bits read lower[w + 1] past the
-// blob, or shift by >= 64.  The encoder writes lower_words == ceil(n * L / 64) and at least n upper bits.
-static inline const char* ef_header_error(const uint8_t* p, uint64_t avail, uint64_t max_n) {
-    if (avail < 32) return "Not enough metadata for EliasFano encoded data";
-    const uint64_t n = rd_u64(p), L = rd_u64(p + 8), lw = rd_u64(p + 16), uw = rd_u64(p + 24);
-    const uint64_t words = (avail - 32) / 8;
-    if (lw > words || uw > words - lw) return "EliasFano list truncated (word counts exceed the blob)";
-    if (L >= 64) return "EliasFano lower_bit_length >= 64";
-    if (n > max_n) return "EliasFano num_elem exceeds the number of vectors";
-    if (n && L && (n > (~0ull) / L || lw < (n * L + 63) / 64)) return "EliasFano lower_words < ceil(num_elem * lower_bit_length / 64)";
-    if (uw > (~0ull) / 64 || uw * 64 < n) return "EliasFano upper stream shorter than num_elem bits";
-    return nullptr;
-}

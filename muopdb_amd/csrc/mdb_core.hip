@@ -420,15 +420,14 @@ extern "C" mdb_status mdb_lane_conforming_distance(mdb_ctx* ctx, const float* a,
 // Q3 seams: PQ quantize / distance
 // ============================================================================================
 mdb_status pq_upload(mdb_ctx* ctx, const mdb_quant_desc* q, PqDev& pq) {
-    if (!q || q->kind != MDB_QUANT_PQ) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "not a product quantizer");
-    if (q->subvector_dimension == 0 || q->dimension % q->subvector_dimension != 0)
-        return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "Vector dimension needs to be divisible by the subvector dimension.");
-    if (q->num_bits == 0 || q->num_bits > 8)
-        return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "PQ codes are u8: num_bits must be 1..8");
-    pq.metric = q->metric; pq.dimension = q->dimension; pq.subdim = q->subvector_dimension; pq.num_bits = q->num_bits;
-    pq.m = pq.dimension / pq.subdim; pq.K = 1 << pq.num_bits;
-    size_t need = (size_t)pq.m * pq.K * pq.subdim;
-    if (!q->codebook || q->codebook_len < need) return mdb_fail(ctx, MDB_ERR_FORMAT, "codebook too short");
+    PqShape sh;   // the descriptor's rules (num_bits must be 1..8, a codebook long enough): pq_shape, mdb_files.cpp
+    {
+        std::string why;
+        const mdb_status st = pq_shape(q, sh, why);
+        if (st != MDB_OK) return mdb_fail(ctx, st, "%s", why.c_str());
+    }
+    pq.metric = sh.metric; pq.dimension = sh.dimension; pq.subdim = sh.subdim; pq.num_bits = sh.num_bits; pq.m = sh.m; pq.K = sh.K;
+    const size_t need = sh.need;
     pq.h_codebook.assign(q->codebook, q->codebook + need);
     if (pq.codebook.alloc(need + 4) != hipSuccess) return mdb_fail(ctx, MDB_ERR_OOM, "codebook alloc");
     MDB_HIP(ctx, hipMemcpyAsync(pq.codebook.p, pq.h_codebook.data(), need * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -4,23 +4,6 @@
 
 #include "mdb_common.h"
 
-// per-user (per-graph) descriptor read by the traversal kernel
-struct HnswUserDev {
-    uint32_t valid;
-    uint32_t n;            // number of vectors (point ids are < n)
-    uint32_t n0;           // number of layer-0 adjacency rows
-    uint32_t num_layers;
-    uint32_t entry_point;  // graph_storage.rs:527-558
-    uint32_t S0, SU;       // fixed row strides of the layer-0 / upper-layer adjacency
-    uint32_t small_layer;  // every layer >= small_layer (> 0) holds <= 64 points and only edges among them; else num_layers
-    uint64_t adj0_off;     // u32 index into the adjacency arena
-    uint64_t adjU_off;
-    uint64_t adjD_off;     // DENSE upper layers: row of (layer, point) at adjD_off + ((layer-1) * n + point) * SU — ~0 when not built
-    uint64_t upper_off;    // index into upper_first[] / level[] (per point)
-    uint64_t vec_off;      // float index into the vector arena (row stride dpad)
-    uint64_t doc_ids_off;  // byte offset of doc id 0 inside the uploaded index bytes
-};
-
 // SPANN: the ratio filter of Spann::search (rs/index/src/spann/index.rs:229-246) applied by the centroid-graph launch itself, in the tail of
 // hnsw_closure_kernel (no launch of its own: 5 us + a gap of a 120 us step).  probes == nullptr: no filter.  done: set by HnswSet::search
 // when the closure kernel served the call (any other traversal kernel: the caller launches spann_filter_kernel).
@@ -32,14 +15,6 @@ struct ClosureFilter {
     const uint8_t* index_bytes = nullptr; // the graph file: a centroid's doc id is its posting-list index
     float ratio = 0.0f;
     bool done = false;
-};
-
-struct HnswBlobInfo {
-    uint32_t quantized_dimension = 0, num_layers = 0;
-    uint64_t edges_len = 0, points_len = 0, edge_offsets_len = 0, level_offsets_len = 0, doc_id_mapping_len = 0;
-    size_t edges_offset = 0, points_offset = 0, edge_offsets_offset = 0, level_offsets_offset = 0, doc_id_mapping_offset = 0;
-    uint64_t num_vectors = 0;
-    size_t vec_data_offset = 0;
 };
 
 // Compact copy of the UPPER layers of one graph (single-index HNSW), built at load for the table path of
@@ -135,8 +110,18 @@ struct HnswSet {
         d_upper_first.borrow(src.d_upper_first); d_level.borrow(src.d_level); d_vecs.borrow(src.d_vecs);
         upper.view_of(src.upper);
     }
+    // hnsw_plan_files (the host half, mdb_files.cpp), then upload
     mdb_status load(mdb_ctx* ctx, const uint8_t* index, size_t index_len, const uint8_t* vectors, size_t vectors_len,
                     const std::vector<std::pair<size_t, size_t>>& offsets, const mdb_quant_desc* quant, uint32_t dimension);
+    // the device half: uploads a plan that hnsw_plan_files made from these files and this descriptor
+    mdb_status upload(mdb_ctx* ctx, const HnswPlan& plan, const uint8_t* index, size_t index_len, const uint8_t* vectors, size_t vectors_len,
+                      const mdb_quant_desc* quant);
+    static HnswPlanOpts plan_opts(const mdb_ctx* c) {   // the load-time switches of the context the plan depends on
+        HnswPlanOpts po;
+        po.no_dense = c->opt.hnsw_no_dense != 0;
+        po.no_table = c->opt.hnsw_no_table != 0;
+        return po;
+    }
     // beam search of every query through its user's graph: device keys [b][k] (distance, point id)
     // ascending + counts.  d_q_user == nullptr => user 0.
     // zero_counters: clear ctx->d_counters[0..15] ahead of the traversal (callers that did not do it themselves)

@@ -30,6 +30,9 @@
 
 #define HNSW_BLOCK 256
 #define HNSW_MAX_STRIDE 256
+// what the kernels below are sized for is what the loader's host half (hnsw_plan_files, mdb_files.cpp) holds a file to: it refuses a
+// node degree above MDB_HNSW_MAX_DEGREE and `o.num_layers > 255` (MDB_HNSW_MAX_LAYERS) with MDB_ERR_UNSUPPORTED
+static_assert(HNSW_MAX_STRIDE == MDB_HNSW_MAX_DEGREE && MDB_HNSW_MAX_LAYERS == 255, "the host half checks other limits than the kernels have");
 
 struct HnswArgs {
     const HnswUserDev* users;
@@ -1373,284 +1376,37 @@ __global__ void pq_rows_kernel(const uint8_t* __restrict__ src, const uint64_t* 
 }
 
 // ------------------------------------------------------------------------------------------ load
-static mdb_status parse_hnsw_blob(mdb_ctx* ctx, const uint8_t* b, size_t len, size_t data_offset, HnswBlobInfo& o) {
-    if (!fits(data_offset, 49, len)) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW index: header out of bounds");
-    const uint8_t* h = b + data_offset;
-    if (h[0] != 0) return mdb_fail(ctx, MDB_ERR_FORMAT, "Unknown version: %d", (int)h[0]);
-    o.quantized_dimension = rd_u32(h + 1);
-    o.num_layers = rd_u32(h + 5);
-    o.edges_len = rd_u64(h + 9);
-    o.points_len = rd_u64(h + 17);
-    o.edge_offsets_len = rd_u64(h + 25);
-    o.level_offsets_len = rd_u64(h + 33);
-    o.doc_id_mapping_len = rd_u64(h + 41);
-    // section lengths come from the file: reject any that cannot fit before forming offsets (overflow-safe)
-    if (o.edges_len > len || o.points_len > len || o.edge_offsets_len > len || o.level_offsets_len > len || o.doc_id_mapping_len > len)
-        return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW index: sections out of bounds");
-    size_t off = data_offset + 49;  // calculate_offsets, graph_storage.rs:170-196
-    o.edges_offset = off + (4 - (off % 4)) % 4;
-    o.points_offset = o.edges_offset + o.edges_len;
-    size_t pe = o.points_offset + o.points_len;
-    o.edge_offsets_offset = pe + (8 - (pe % 8)) % 8;
-    o.level_offsets_offset = o.edge_offsets_offset + o.edge_offsets_len;
-    size_t le = o.level_offsets_offset + o.level_offsets_len;
-    o.doc_id_mapping_offset = le + (16 - (le % 16)) % 16;
-    if (o.doc_id_mapping_offset + o.doc_id_mapping_len > len) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW index: sections out of bounds");
-    if (o.num_layers > 255) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "more than 255 HNSW layers");
-    if (o.level_offsets_len / 8 < (uint64_t)o.num_layers + 1 && o.num_layers > 0)
-        return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW index: level_offsets too short");
-    return MDB_OK;
-}
-
+// The host half — header and section parse, every range check, adjacency, levels and the compact upper layers — is
+// hnsw_plan_files (mdb_files.cpp): nothing below it reads a file field that it has not bounded.
 mdb_status HnswSet::load(mdb_ctx* ctx_, const uint8_t* index, size_t index_len, const uint8_t* vectors, size_t vectors_len,
                          const std::vector<std::pair<size_t, size_t>>& offsets, const mdb_quant_desc* quant, uint32_t dim) {
+    HnswPlan plan;
+    std::string why;
+    const mdb_status st = hnsw_plan_files(index, index_len, vectors, vectors_len, offsets, quant, dim, plan_opts(ctx_), plan, why);
+    if (st != MDB_OK) return mdb_fail(ctx_, st, "%s", why.c_str());
+    return upload(ctx_, plan, index, index_len, vectors, vectors_len, quant);
+}
+
+mdb_status HnswSet::upload(mdb_ctx* ctx_, const HnswPlan& plan, const uint8_t* index, size_t index_len, const uint8_t* vectors,
+                           size_t vectors_len, const mdb_quant_desc* quant) {
     ctx = ctx_;
-    kind = quant ? (int)quant->kind : MDB_QUANT_NONE;
-    metric = quant ? quant->metric : MDB_METRIC_L2;
-    if (kind == MDB_QUANT_PQ) {
-        MDB_TRY(pq_upload(ctx, quant, pq));
-        if ((uint32_t)pq.dimension != dim) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "PQ dimension %d != %u", pq.dimension, dim);
-    }
-    // bytes of one stored vector in the file: f32 row, or m u8 codes (BlockBasedHnsw<ProductQuantizer>)
-    const size_t file_row = kind == MDB_QUANT_PQ ? (size_t)pq.m : (size_t)dim * 4;
-    const uint32_t file_qdim = kind == MDB_QUANT_PQ ? (uint32_t)pq.m : dim;
-    dimension = dim;
-    dpad = ((int)dim + 3) / 4 * 4;
-    const size_t U = offsets.size();
-    blobs.resize(U);
-    h_users.assign(U + 1, HnswUserDev{});  // [U] = sentinel (valid = 0): unknown user => None
-    std::vector<uint32_t> h_adj, h_upper_first;
-    std::vector<uint8_t> h_level;
-    std::vector<uint64_t> row_src;
-    for (size_t ui = 0; ui < U; ++ui) {
-        HnswBlobInfo& bi = blobs[ui];
-        MDB_TRY(parse_hnsw_blob(ctx, index, index_len, offsets[ui].first, bi));
-        if (bi.quantized_dimension != file_qdim) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW quantized_dimension %u != %u", bi.quantized_dimension, file_qdim);
-        size_t voff = offsets[ui].second;
-        if (!fits(voff, 8, vectors_len)) return mdb_fail(ctx, MDB_ERR_FORMAT, "vector file: header out of bounds");
-        uint64_t nv = rd_u64(vectors + voff);
-        if (file_row == 0 || nv > (vectors_len - voff - 8) / file_row) return mdb_fail(ctx, MDB_ERR_FORMAT, "vector file truncated");
-        if (kind != MDB_QUANT_PQ && (voff + 8) % 4 != 0) return mdb_fail(ctx, MDB_ERR_FORMAT, "f32 vector file is not 4-byte aligned");
-        if (nv > 0xFFFFFFFEull) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "point ids are u32");
-        bi.num_vectors = nv;
-        bi.vec_data_offset = voff + 8;
-        HnswUserDev& u = h_users[ui];
-        u.valid = 1;
-        u.n = (uint32_t)nv;
-        u.num_layers = bi.num_layers;
-        u.doc_ids_off = bi.doc_id_mapping_offset;
-        u.vec_off = (uint64_t)row_src.size() * dpad;
-        for (uint64_t r = 0; r < nv; ++r) row_src.push_back(bi.vec_data_offset + r * file_row);
-        u.upper_off = h_level.size();
-        h_level.resize(h_level.size() + nv, 0);
-        h_upper_first.resize(h_upper_first.size() + nv, 0xFFFFFFFFu);
-        if (bi.num_layers == 0) continue;
-        const uint32_t nl = bi.num_layers;
-        auto lvl = [&](size_t i) { return rd_u64(index + bi.level_offsets_offset + i * 8); };
-        auto eo = [&](size_t i) { return rd_u64(index + bi.edge_offsets_offset + i * 8); };
-        auto pt = [&](size_t i) { return rd_u32(index + bi.points_offset + i * 4); };
-        auto ed = [&](size_t i) { return rd_u32(index + bi.edges_offset + i * 4); };
-        const size_t n_eo = bi.edge_offsets_len / 8, n_pts = bi.points_len / 4, n_edges = bi.edges_len / 4;
-        for (uint32_t i = 0; i <= nl; ++i)
-            if (lvl(i) > n_eo) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW level offset out of bounds");
-        // entry point (graph_storage.rs:527-558)
-        if (nl == 1) {
-            size_t num_points = n_eo ? n_eo - 1 : 0;
-            u.entry_point = 0;
-            for (size_t i = 0; i < num_points; ++i)
-                if (eo(i + 1) > eo(i)) { u.entry_point = (uint32_t)i; break; }
-        } else {
-            if (lvl(0) >= n_pts) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW top layer is empty");
-            u.entry_point = pt(lvl(0));
-        }
-        // layer 0: slots s0 .. e0 (the last one is the sentinel)
-        const size_t s0 = lvl(nl - 1), e0 = lvl(nl);
-        const size_t n0 = e0 > s0 ? e0 - s0 - 1 : 0;
-        u.n0 = (uint32_t)std::min<size_t>(n0, nv);
-        uint32_t S0 = 1;
-        for (size_t p = 0; p < u.n0; ++p) {
-            uint64_t a0 = eo(s0 + p), a1 = eo(s0 + p + 1);
-            if (a1 < a0 || a1 > n_edges) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW edge offsets corrupt");
-            S0 = std::max<uint32_t>(S0, (uint32_t)std::min<uint64_t>(a1 - a0, 1u << 20));
-        }
-        // upper layers: per point level + rows
-        uint32_t SU = 1;
-        for (uint32_t layer = 1; layer < nl; ++layer) {
-            size_t s = lvl(nl - 1 - layer), e = lvl(nl - layer);
-            if (e > n_pts + 0 && layer > 0 && e > n_pts) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW points section too short");
-            for (size_t i = s; i < e; ++i) {
-                uint32_t p = pt(i);
-                if (p >= nv) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW upper-layer point id out of range");
-                h_level[u.upper_off + p] = std::max<uint8_t>(h_level[u.upper_off + p], (uint8_t)layer);
-                uint64_t a0 = eo(i), a1 = eo(i + 1);
-                if (a1 < a0 || a1 > n_edges) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW edge offsets corrupt");
-                SU = std::max<uint32_t>(SU, (uint32_t)std::min<uint64_t>(a1 - a0, 1u << 20));
-            }
-        }
-        if (S0 > HNSW_MAX_STRIDE || SU > HNSW_MAX_STRIDE)
-            return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "node degree %u exceeds %d", std::max(S0, SU), HNSW_MAX_STRIDE);
-        u.S0 = S0;
-        u.SU = SU;
-        max_stride = std::max(max_stride, std::max(S0, SU));
-        u.adj0_off = h_adj.size();
-        h_adj.resize(h_adj.size() + (size_t)u.n0 * S0, 0xFFFFFFFFu);
-        for (size_t p = 0; p < u.n0; ++p) {
-            uint64_t a0 = eo(s0 + p), a1 = eo(s0 + p + 1);
-            for (uint64_t x = a0; x < a1; ++x) {
-                const uint32_t e = ed(x);
-                if (e >= nv) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW edge %u of point %zu is outside the vector storage (%llu vectors)", e, p, (unsigned long long)nv);
-                h_adj[u.adj0_off + p * S0 + (x - a0)] = e;
-            }
-        }
-        // rows of the upper layers
-        uint32_t rows = 0;
-        for (uint64_t p = 0; p < nv; ++p)
-            if (h_level[u.upper_off + p]) { h_upper_first[u.upper_off + p] = rows; rows += h_level[u.upper_off + p]; }
-        u.adjU_off = h_adj.size();
-        h_adj.resize(h_adj.size() + (size_t)rows * SU, 0xFFFFFFFFu);
-        std::vector<uint8_t> filled((size_t)rows, 0);
-        for (uint32_t layer = 1; layer < nl; ++layer) {
-            size_t s = lvl(nl - 1 - layer), e = lvl(nl - layer);
-            for (size_t i = s; i < e; ++i) {
-                uint32_t p = pt(i);
-                size_t r = (size_t)h_upper_first[u.upper_off + p] + (layer - 1);
-                if (filled[r]) continue;  // find_point_in_range returns the FIRST match
-                filled[r] = 1;
-                uint64_t a0 = eo(i), a1 = eo(i + 1);
-                for (uint64_t x = a0; x < a1; ++x) {
-                    const uint32_t e = ed(x);
-                    if (e >= nv) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW upper-layer edge %u is outside the vector storage", e);
-                    h_adj[u.adjU_off + r * SU + (x - a0)] = e;
-                }
-            }
-        }
-        // dense upper layers (hnsw_upper_row): every (layer, point) gets a row slot — affordable up to 1 GiB per graph
-        u.adjD_off = ~0ull;
-        if (nl > 1 && !ctx->opt.hnsw_no_dense && (uint64_t)(nl - 1) * nv * SU * 4 <= ((uint64_t)1 << 30)) {
-            u.adjD_off = h_adj.size();
-            h_adj.resize(h_adj.size() + (size_t)(nl - 1) * nv * SU, 0xFFFFFFFFu);
-            for (uint64_t p = 0; p < nv; ++p) {
-                const uint32_t lv = h_level[u.upper_off + p];
-                for (uint32_t layer = 1; layer <= lv && layer < nl; ++layer) {
-                    const size_t r = (size_t)h_upper_first[u.upper_off + p] + (layer - 1);
-                    std::copy(h_adj.begin() + u.adjU_off + r * SU, h_adj.begin() + u.adjU_off + (r + 1) * SU,
-                              h_adj.begin() + u.adjD_off + ((size_t)(layer - 1) * nv + p) * SU);
-                }
-            }
-        }
-        // tiny top layers (hnsw_beam_kernel expands them frontier-wise): <= 64 points, every edge inside the layer
-        {
-            std::vector<uint64_t> cnt(nl + 1, 0);
-            for (uint64_t p = 0; p < nv; ++p) cnt[std::min<uint32_t>(h_level[u.upper_off + p], nl)] += 1;
-            for (int l = (int)nl - 1; l >= 0; --l) cnt[l] += cnt[l + 1];  // cnt[l] = points with level >= l
-            uint32_t small = nl;
-            for (uint32_t layer = nl; layer-- > 1;) {
-                bool ok = cnt[layer] <= 64;
-                if (ok) {
-                    size_t s = lvl(nl - 1 - layer), e = lvl(nl - layer);
-                    for (size_t i = s; i < e && ok; ++i) {
-                        uint64_t a0 = eo(i), a1 = eo(i + 1);
-                        for (uint64_t x = a0; x < a1; ++x)
-                            if (h_level[u.upper_off + ed(x)] < layer) { ok = false; break; }
-                    }
-                }
-                if (!ok) break;
-                small = layer;
-            }
-            u.small_layer = small;
-        }
-        max_n = std::max(max_n, u.n);
-        max_rows0 = std::max<uint64_t>(max_rows0, std::min<uint64_t>((uint64_t)u.n0 * u.S0, 0xFFFFFFFFull));
-        if (u.num_layers > 1) {
-            if (u.adjD_off == ~0ull) all_dense = false;
-            max_rowsU = std::max<uint64_t>(max_rowsU, std::min<uint64_t>((uint64_t)(u.num_layers - 1) * u.n * u.SU, 0xFFFFFFFFull));
-        }
-    }
+    kind = plan.kind;
+    metric = plan.metric;
+    if (kind == MDB_QUANT_PQ) MDB_TRY(pq_upload(ctx, quant, pq));
+    const uint32_t dim = dimension = plan.dimension;
+    dpad = plan.dpad;
+    const size_t U = plan.blobs.size();
+    blobs = plan.blobs;
+    h_users = plan.users;
+    max_n = plan.max_n; max_stride = plan.max_stride; max_rows0 = plan.max_rows0; max_rowsU = plan.max_rowsU; all_dense = plan.all_dense;
+    const std::vector<uint32_t>&h_adj = plan.adj, &h_upper_first = plan.upper_first, &h_cids = plan.cids, &h_crows = plan.crows,
+                               &h_crows2 = plan.crows2, &h_map21 = plan.map21;
+    const std::vector<uint8_t>& h_level = plan.level;
+    const std::vector<uint64_t>& row_src = plan.row_src;
+    const std::vector<float>&h_cvecs = plan.cvecs, &h_cvecs2 = plan.cvecs2;
     total_rows = row_src.size();
-    // ---- the table path's compact upper layers (mdb_hnsw_upper.hip): one graph, >= 2 layers, f32 rows, rows of <= 64 edges
-    std::vector<uint32_t> h_cids, h_crows, h_crows2, h_map21;
-    std::vector<float> h_cvecs, h_cvecs2;
-    upper.nu = 0;
-    if (U == 1 && kind != MDB_QUANT_PQ && !ctx->opt.hnsw_no_table && h_users[0].num_layers >= 2 && h_users[0].SU <= 64 &&
-        h_users[0].n > 0) {
-        const HnswUserDev& u = h_users[0];
-        const HnswBlobInfo& bi = blobs[0];
-        const uint32_t nl = u.num_layers, SU = u.SU;
-        // compact set: every point on a layer >= 1 and every target of an upper-layer edge (a target that is not on the layer
-        // itself has an empty row there, as in the dense form)
-        std::vector<uint8_t> in_set(u.n, 0);
-        for (uint64_t p = 0; p < u.n; ++p)
-            if (h_level[u.upper_off + p]) in_set[p] = 1;
-        for (uint64_t p = 0; p < u.n; ++p) {
-            const uint32_t lv = h_level[u.upper_off + p];
-            for (uint32_t layer = 1; layer <= lv && layer < nl; ++layer) {
-                const size_t r = (size_t)h_upper_first[u.upper_off + p] + (layer - 1);
-                for (uint32_t t = 0; t < SU; ++t) {
-                    const uint32_t e = h_adj[u.adjU_off + r * SU + t];
-                    if (e != 0xFFFFFFFFu) in_set[e] = 1;
-                }
-            }
-        }
-        std::vector<uint32_t> cidx(u.n, 0xFFFFFFFFu);
-        for (uint64_t p = 0; p < u.n; ++p)
-            if (in_set[p]) { cidx[p] = (uint32_t)h_cids.size(); h_cids.push_back((uint32_t)p); }
-        const size_t nu = h_cids.size();
-        // affordable: rows (nl-1) * nu * SU words, vectors nu * d floats — a small fraction of the graph unless it is degenerate
-        if (nu > 0 && nu <= ((size_t)1 << 22) && nu * 4 <= (size_t)u.n + 4096 && in_set[u.entry_point]) {
-            h_crows.assign((size_t)(nl - 1) * nu * SU, 0xFFFFFFFFu);
-            for (size_t c = 0; c < nu; ++c) {
-                const uint32_t p = h_cids[c];
-                const uint32_t lv = h_level[u.upper_off + p];
-                for (uint32_t layer = 1; layer <= lv && layer < nl; ++layer) {
-                    const size_t r = (size_t)h_upper_first[u.upper_off + p] + (layer - 1);
-                    for (uint32_t t = 0; t < SU; ++t) {
-                        const uint32_t e = h_adj[u.adjU_off + r * SU + t];
-                        h_crows[((size_t)(layer - 1) * nu + c) * SU + t] = e == 0xFFFFFFFFu ? e : cidx[e];
-                    }
-                }
-            }
-            h_cvecs.resize(nu * (size_t)dim);
-            for (size_t c = 0; c < nu; ++c)
-                memcpy(&h_cvecs[c * (size_t)dim], vectors + bi.vec_data_offset + (size_t)h_cids[c] * file_row, (size_t)dim * 4);
-            upper.nu = (uint32_t)nu;
-            upper.su = SU;
-            upper.layers = nl - 1;
-            upper.small_layer = u.small_layer;
-            upper.entry_c = cidx[u.entry_point];
-            // the TOP set: points on a layer >= 2 and the targets of those layers' edges
-            upper.nu2 = 0;
-            if (nl >= 3) {
-                std::vector<uint8_t> in2(nu, 0);
-                for (size_t c = 0; c < nu; ++c) {
-                    const uint32_t lv = h_level[u.upper_off + h_cids[c]];
-                    if (lv >= 2) in2[c] = 1;
-                    for (uint32_t layer = 2; layer <= lv && layer < nl; ++layer)
-                        for (uint32_t t = 0; t < SU; ++t) {
-                            const uint32_t e = h_crows[((size_t)(layer - 1) * nu + c) * SU + t];
-                            if (e != 0xFFFFFFFFu) in2[e] = 1;
-                        }
-                }
-                std::vector<uint32_t> c2of(nu, 0xFFFFFFFFu);
-                for (size_t c = 0; c < nu; ++c)
-                    if (in2[c]) { c2of[c] = (uint32_t)h_map21.size(); h_map21.push_back((uint32_t)c); }
-                const size_t nu2 = h_map21.size();
-                if (nu2 > 0 && nu2 <= 16384 && in2[upper.entry_c]) {
-                    h_crows2.assign((size_t)(nl - 2) * nu2 * SU, 0xFFFFFFFFu);
-                    for (size_t c2 = 0; c2 < nu2; ++c2)
-                        for (uint32_t layer = 2; layer < nl; ++layer)
-                            for (uint32_t t = 0; t < SU; ++t) {
-                                const uint32_t e = h_crows[((size_t)(layer - 1) * nu + h_map21[c2]) * SU + t];
-                                h_crows2[((size_t)(layer - 2) * nu2 + c2) * SU + t] = e == 0xFFFFFFFFu ? e : c2of[e];
-                            }
-                    h_cvecs2.resize(nu2 * (size_t)dim);
-                    for (size_t c2 = 0; c2 < nu2; ++c2)
-                        memcpy(&h_cvecs2[c2 * (size_t)dim], &h_cvecs[(size_t)h_map21[c2] * dim], (size_t)dim * 4);
-                    upper.nu2 = (uint32_t)nu2;
-                    upper.entry_c2 = c2of[upper.entry_c];
-                }
-            }
-        }
-    }
+    upper.nu = plan.nu; upper.su = plan.su; upper.layers = plan.layers; upper.small_layer = plan.small_layer; upper.entry_c = plan.entry_c;
+    upper.nu2 = plan.nu2; upper.entry_c2 = plan.entry_c2;
     // ---- uploads
     DevBuf<uint8_t> d_vec;
     DevBuf<uint64_t> d_row_src;
@@ -1892,8 +1648,12 @@ mdb_status mdb_hnsw_load(mdb_ctx* ctx, const void* index_bytes, size_t index_len
     if (!ctx || !index_bytes || !vectors_bytes || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
     MDB_ENTER(ctx);
-    if ((size_t)index_offset + 9 > index_len) return mdb_fail(ctx, MDB_ERR_FORMAT, "HNSW index: header out of bounds");
-    uint32_t dim = quant && quant->dimension ? quant->dimension : rd_u32((const uint8_t*)index_bytes + index_offset + 1);
+    uint32_t dim = 0;
+    {
+        std::string why;
+        const mdb_status st = hnsw_file_dimension((const uint8_t*)index_bytes, index_len, index_offset, quant, &dim, why);
+        if (st != MDB_OK) return mdb_fail(ctx, st, "%s", why.c_str());
+    }
     mdb_hnsw* h = new mdb_hnsw();
     mdb_status st = h->set.load(ctx, (const uint8_t*)index_bytes, index_len, (const uint8_t*)vectors_bytes, vectors_len,
                                 {{index_offset, vectors_offset}}, quant, dim);

@@ -9,26 +9,6 @@
 #include "mdb_common.h"
 #include "mdb_kernels.h"
 
-// per-user (per-blob) descriptor read by the kernels
-struct IvfUserDev {
-    uint32_t valid;           // 0 for an unknown user (search returns None)
-    uint32_t list_base;       // global index of the user's list 0
-    uint32_t num_lists;       // = num_clusters
-    uint32_t num_vectors;
-    uint32_t tomb_base;       // word offset into the tombstone arena
-    uint32_t cent_tile_base;  // first tile of the user's centroids in the centroid tile arena
-    uint64_t doc_ids_off;     // byte offset of doc id 0 inside the uploaded index bytes
-};
-
-// host-side parse of one blob (rs/index/src/ivf/block_based/storage.rs:52-138)
-struct IvfBlobInfo {
-    uint32_t num_features = 0, quantized_dimension = 0, num_clusters = 0;
-    uint64_t num_vectors = 0, num_posting_lists = 0;
-    size_t doc_id_mapping_offset = 0, centroid_offset = 0, pl_metadata_offset = 0, pl_start_offset = 0;
-    uint64_t vec_num_vectors = 0;
-    size_t vec_data_offset = 0;
-};
-
 struct U128Key {
     uint64_t lo, hi;
     bool operator==(const U128Key& o) const { return lo == o.lo && hi == o.hi; }
@@ -101,9 +81,18 @@ struct IvfSet {
     // set to false BEFORE load by owners whose centroids are searched by a graph (Spann: spann/index.rs:211-228 — coarse() and
     // search_fused are never reached): the load then skips the coarse search's accelerator copies (CoarseMfma: ~1.5 x the centroids)
     bool coarse_by_scan = true;
+    // ivf_plan_files (the host half, mdb_files.cpp), then upload
     mdb_status load(mdb_ctx* ctx, const uint8_t* index, size_t index_len, const uint8_t* vectors, size_t vectors_len,
                     const std::vector<std::pair<size_t, size_t>>& offsets, const mdb_quant_desc* quant,
                     uint32_t shard_rank, uint32_t shard_world);
+    // the device half: uploads a plan that ivf_plan_files made from these files and this descriptor
+    mdb_status upload(mdb_ctx* ctx, const IvfPlan& plan, const uint8_t* index, size_t index_len, const uint8_t* vectors, size_t vectors_len,
+                      const mdb_quant_desc* quant);
+    static IvfPlanOpts plan_opts(const mdb_ctx* c) {   // the load-time switch of the context the plan depends on
+        IvfPlanOpts po;
+        po.pad_units = (uint32_t)std::min<long long>(MDB_UPT, std::max<long long>(1, c->opt.ivf_list_pad_units));
+        return po;
+    }
     mdb_status build_doc_map(size_t ui, mdb_ctx* ectx);
     mdb_status invalidate(size_t ui, const mdb_u128* doc_ids, size_t n, uint8_t* flags_out, bool test_only);
     // single index with >= 64K centroids: sample / centred copy for the batched (MFMA-filtered) coarse search

@@ -30,152 +30,40 @@
 #include "mdb_ivf_merge.hip.h"
 
 // ------------------------------------------------------------------------------------------ IvfSet: load
-static mdb_status parse_ivf_blob(mdb_ctx* ctx, const uint8_t* b, size_t len, size_t offset, IvfBlobInfo& o) {
-    if (!fits(offset, 45, len)) return mdb_fail(ctx, MDB_ERR_FORMAT, "IVF index: header out of bounds");
-    const uint8_t* h = b + offset;
-    if (h[0] != 0) return mdb_fail(ctx, MDB_ERR_FORMAT, "Unknown version: %d", (int)h[0]);
-    o.num_features = rd_u32(h + 1);
-    o.quantized_dimension = rd_u32(h + 5);
-    o.num_clusters = rd_u32(h + 9);
-    o.num_vectors = rd_u64(h + 13);
-    uint64_t doc_len = rd_u64(h + 21), cent_len = rd_u64(h + 29);
-    o.doc_id_mapping_offset = offset + align_up(45, 16);                 // storage.rs:66-67
-    // every section length comes from the file: all sums below are overflow-checked against the blob length
-    if (!fits(o.doc_id_mapping_offset, doc_len, len - 8)) return mdb_fail(ctx, MDB_ERR_FORMAT, "IVF index: doc-id section out of bounds");
-    o.centroid_offset = align_up(o.doc_id_mapping_offset + doc_len, 8);  // :69-72
-    if (!fits(o.centroid_offset, cent_len, len - 8)) return mdb_fail(ctx, MDB_ERR_FORMAT, "IVF index: centroid section out of bounds");
-    size_t meta = align_up(o.centroid_offset + cent_len, 8);             // :74-75
-    if (!fits(meta, 8, len)) return mdb_fail(ctx, MDB_ERR_FORMAT, "IVF index: metadata out of bounds");
-    o.num_posting_lists = rd_u64(b + meta);
-    o.pl_metadata_offset = meta + 8;
-    if (o.num_posting_lists > (len - o.pl_metadata_offset) / 16) return mdb_fail(ctx, MDB_ERR_FORMAT, "IVF index: posting lists out of bounds");
-    o.pl_start_offset = o.pl_metadata_offset + o.num_posting_lists * 16;  // :80-82
-    if (o.num_vectors > 0xFFFFFFFEull) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "point ids are u32");
-    if (!fits(o.doc_id_mapping_offset + 16, o.num_vectors * 16, len) ||
-        (uint64_t)o.num_clusters * o.num_features > (len / 4) || !fits(o.centroid_offset + 8, (uint64_t)o.num_clusters * o.num_features * 4, len))
-        return mdb_fail(ctx, MDB_ERR_FORMAT, "IVF index: sections out of bounds");
-    return MDB_OK;
-}
-
+// The host half — container parse, every range check, list ownership and the tile tables — is ivf_plan_files (mdb_files.cpp):
+// nothing below it reads a file field that it has not bounded.
 mdb_status IvfSet::load(mdb_ctx* ctx_, const uint8_t* index, size_t index_len, const uint8_t* vectors, size_t vectors_len,
                         const std::vector<std::pair<size_t, size_t>>& offsets, const mdb_quant_desc* quant,
                         uint32_t shard_rank, uint32_t shard_world) {
+    IvfPlan plan;
+    std::string why;
+    const mdb_status st = ivf_plan_files(index, index_len, vectors, vectors_len, offsets, quant, shard_rank, shard_world, plan_opts(ctx_), plan, why);
+    if (st != MDB_OK) return mdb_fail(ctx_, st, "%s", why.c_str());
+    return upload(ctx_, plan, index, index_len, vectors, vectors_len, quant);
+}
+
+mdb_status IvfSet::upload(mdb_ctx* ctx_, const IvfPlan& plan, const uint8_t* index, size_t index_len, const uint8_t* vectors,
+                          size_t vectors_len, const mdb_quant_desc* quant) {
     ctx = ctx_;
-    if (shard_world == 0) shard_world = 1;
-    if (shard_rank >= shard_world) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "shard_rank >= shard_world");
-    kind = quant ? quant->kind : MDB_QUANT_NONE;
-    metric = quant ? quant->metric : MDB_METRIC_L2;
-    const size_t U = offsets.size();
-    blobs.resize(U);
-    h_users.assign(U + 1, IvfUserDev{});  // [U] = sentinel (valid = 0): unknown user => None
-    std::vector<uint64_t> list_byte_off;   // per global list (or ~0 when not owned / empty)
-    std::vector<uint32_t> list_len;
-    std::vector<uint32_t> h_list_tile_off(1, 0);
-    std::vector<uint64_t> tile_src;        // per tile (f32 lists: per 32-slot unit): byte offset of the user's vector 0
-    std::vector<uint32_t> tile_limit;      // per tile (unit): user's num_vectors
-    std::vector<uint32_t> unit_desc;       // f32 lists: gather_f32_units_kernel's unit descriptors
-    const bool units = (quant ? quant->kind : MDB_QUANT_NONE) != MDB_QUANT_PQ;   // f32 lists: list_tile_off counts 16-slot units
-    size_t wave_tiles = 0;
-    const uint32_t pad_units = (uint32_t)std::min<long long>(MDB_UPT, std::max<long long>(1, ctx->opt.ivf_list_pad_units));
-    std::vector<uint64_t> cent_tile_src;
-    std::vector<uint32_t> cent_tile_first, cent_tile_limit;
-    size_t tomb_words = 0;
-    // list ownership for the multi-GPU path.  Multi-user collections: list l of every user -> rank l % world
-    // (a user's ~150 lists spread evenly whatever their sizes).  ONE index (C5: 65 536 lists of very different lengths):
-    // size-balanced — lists taken longest first (ties: lower index), each to the least loaded rank (ties: lower rank);
-    // every rank parses the same file, so every rank computes the same map.
-    std::vector<uint32_t> balanced_owner;
-    if (U == 1 && shard_world > 1) {
-        IvfBlobInfo b0;
-        MDB_TRY(parse_ivf_blob(ctx, index, index_len, offsets[0].first, b0));
-        std::vector<std::pair<uint64_t, uint32_t>> order;  // (num_elem, list)
-        for (uint32_t l = 0; l < b0.num_clusters && l < b0.num_posting_lists; ++l) {
-            const uint8_t* md = index + b0.pl_metadata_offset + (size_t)l * 16;
-            const uint64_t rel = rd_u64(md + 8);
-            uint64_t ne = 0;
-            if (fits(b0.pl_start_offset, rel, index_len) && fits(b0.pl_start_offset + rel, 32, index_len)) ne = rd_u64(index + b0.pl_start_offset + rel);
-            order.push_back({ne, l});
-        }
-        std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-        std::vector<uint64_t> load(shard_world, 0);
-        balanced_owner.assign(order.size(), 0);
-        for (auto& e : order) {
-            uint32_t r = 0;
-            for (uint32_t i = 1; i < shard_world; ++i) if (load[i] < load[r]) r = i;
-            balanced_owner[e.second] = r;
-            load[r] += e.first;
-        }
-    }
-    for (size_t ui = 0; ui < U; ++ui) {
-        IvfBlobInfo& bi = blobs[ui];
-        MDB_TRY(parse_ivf_blob(ctx, index, index_len, offsets[ui].first, bi));
-        if (ui == 0) { num_features = bi.num_features; quantized_dimension = bi.quantized_dimension; }
-        if (bi.num_features != num_features || bi.quantized_dimension != quantized_dimension)
-            return mdb_fail(ctx, MDB_ERR_FORMAT, "users disagree on num_features / quantized_dimension");
-        if (bi.num_posting_lists != bi.num_clusters)
-            return mdb_fail(ctx, MDB_ERR_FORMAT, "Mismatch between number of clusters (%u) and number of posting lists (%zu)",
-                            bi.num_clusters, (size_t)bi.num_posting_lists);
-        const size_t esz = kind == MDB_QUANT_PQ ? 1 : 4;
-        size_t voff = offsets[ui].second;
-        if (!fits(voff, 8, vectors_len)) return mdb_fail(ctx, MDB_ERR_FORMAT, "vector file: header out of bounds");
-        uint64_t nv = rd_u64(vectors + voff);  // async_storage.rs:83-87
-        const uint64_t row_bytes = (uint64_t)quantized_dimension * esz;
-        if (row_bytes == 0 || nv > (vectors_len - voff - 8) / row_bytes)
-            return mdb_fail(ctx, MDB_ERR_FORMAT, "vector file: %zu vectors of %u x %zu B exceed the file", (size_t)nv,
-                            quantized_dimension, esz);
-        bi.vec_num_vectors = nv;
-        bi.vec_data_offset = voff + 8;
-        IvfUserDev& u = h_users[ui];
-        u.valid = 1;
-        u.list_base = (uint32_t)list_len.size();
-        u.num_lists = bi.num_clusters;
-        u.num_vectors = (uint32_t)bi.num_vectors;
-        u.doc_ids_off = bi.doc_id_mapping_offset + 16;
-        u.tomb_base = (uint32_t)tomb_words;
-        tomb_words += (std::max<uint64_t>(bi.num_vectors, nv) + 31) / 32 + 1;
-        max_user_vectors = std::max<uint64_t>(max_user_vectors, std::max<uint64_t>(bi.num_vectors, nv));
-        if (user_points.size() <= ui) user_points.resize(ui + 1, 0);
-        user_points[ui] = std::max<uint64_t>(bi.num_vectors, nv);
-        u.cent_tile_base = (uint32_t)cent_tile_src.size();
-        for (uint32_t c0 = 0; c0 < bi.num_clusters; c0 += MDB_TILE) {
-            cent_tile_src.push_back(bi.centroid_offset + 8);
-            cent_tile_first.push_back(c0);
-            cent_tile_limit.push_back(bi.num_clusters);
-        }
-        for (uint32_t l = 0; l < bi.num_clusters; ++l) {
-            const uint8_t* md = index + bi.pl_metadata_offset + (size_t)l * 16;
-            const uint64_t rel = rd_u64(md + 8);
-            if (!fits(bi.pl_start_offset, rel, index_len) || !fits(bi.pl_start_offset + rel, 32, index_len))
-                return mdb_fail(ctx, MDB_ERR_FORMAT, "posting list %u out of bounds", l);
-            size_t pl_off = rel + bi.pl_start_offset;  // storage.rs:293-294
-            if (const char* why = ef_header_error(index + pl_off, index_len - pl_off, std::max<uint64_t>(bi.num_vectors, nv)))
-                return mdb_fail(ctx, MDB_ERR_FORMAT, "posting list %u: %s", l, why);
-            uint64_t ne = rd_u64(index + pl_off);
-            if (pl_off % 8 != 0) return mdb_fail(ctx, MDB_ERR_FORMAT, "posting list %u is not 8-byte aligned", l);
-            bool owned = balanced_owner.empty() ? (l % shard_world) == shard_rank : balanced_owner[l] == shard_rank;
-            if (!owned) ne = 0;
-            if (ne > 0xFFFFFFFFull) return mdb_fail(ctx, MDB_ERR_FORMAT, "posting list too long");
-            list_byte_off.push_back(ne ? pl_off : ~0ull);
-            list_len.push_back((uint32_t)ne);
-            uint32_t nt = (uint32_t)((ne + MDB_TILE - 1) / MDB_TILE);
-            wave_tiles += nt;
-            if (units) {   // ceil(ne / 16) units: whole tiles of four, then a narrow tail of 1..3
-                nt = (uint32_t)((ne + MDB_UNIT - 1) / MDB_UNIT);
-                nt = (nt + pad_units - 1) / pad_units * pad_units;   // MDB_IVF_LIST_PAD_UNITS: 1 (16 slots) | 2 | 4 (= the 64-slot tiles of rounds 1-5)
-                const uint32_t u0 = h_list_tile_off.back(), whole = nt & ~(uint32_t)(MDB_UPT - 1), tail = nt - whole;
-                for (uint32_t t = 0; t < nt; ++t)
-                    unit_desc.push_back(((u0 + (t & ~(uint32_t)(MDB_UPT - 1))) << 4) | ((t & (MDB_UPT - 1)) << 2) | (t >= whole ? tail : 0u));
-            }
-            for (uint32_t t = 0; t < nt; ++t) { tile_src.push_back(bi.vec_data_offset); tile_limit.push_back((uint32_t)nv); }
-            h_list_tile_off.push_back(h_list_tile_off.back() + nt);
-            total_slots_valid += ne;
-        }
-    }
+    kind = plan.kind;
+    metric = plan.metric;
+    num_features = plan.num_features;
+    quantized_dimension = plan.quantized_dimension;
+    const size_t U = plan.blobs.size();
+    blobs = plan.blobs;
+    h_users = plan.users;
+    max_user_vectors = plan.max_user_vectors;
+    user_points = plan.user_points;
+    total_slots_valid = plan.total_slots_valid;
+    const std::vector<uint64_t>&list_byte_off = plan.list_byte_off, &tile_src = plan.tile_src, &cent_tile_src = plan.cent_tile_src;
+    const std::vector<uint32_t>&list_len = plan.list_len, &h_list_tile_off = plan.list_tile_off, &tile_limit = plan.tile_limit,
+                               &unit_desc = plan.unit_desc, &cent_tile_first = plan.cent_tile_first, &cent_tile_limit = plan.cent_tile_limit;
+    const bool units = plan.units;   // f32 lists: list_tile_off counts 16-slot units
+    const size_t tomb_words = plan.tomb_words;
     G = list_len.size();
     const size_t ntiles = h_list_tile_off.back();   // (f32 lists: units)
     const size_t slots_per = units ? MDB_UNIT : MDB_TILE;
-    total_tiles = wave_tiles;
-    if (ntiles > (units ? 0x0FFFFFFFull : 0x7FFFFFFFull / MDB_TILE)) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "too many posting-list slots");
+    total_tiles = plan.wave_tiles;
     // ---- uploads
     DevBuf<uint8_t> d_vec;
     if (d_index.alloc(index_len + 16) != hipSuccess || d_vec.alloc(vectors_len + 16) != hipSuccess)
@@ -236,8 +124,6 @@ mdb_status IvfSet::load(mdb_ctx* ctx_, const uint8_t* index, size_t index_len, c
                 }
             }
         }
-        if ((uint32_t)pq.m != quantized_dimension) return mdb_fail(ctx, MDB_ERR_FORMAT, "quantized_dimension != dimension / subvector_dimension");
-        if ((uint32_t)pq.dimension != num_features) return mdb_fail(ctx, MDB_ERR_FORMAT, "quantizer dimension != num_features");
         mw = (pq.m + 3) / 4;
         size_t total = ntiles * MDB_TILE * (size_t)mw;
         if (d_codes.alloc(total + 4) != hipSuccess) return mdb_fail(ctx, MDB_ERR_OOM, "code tiles alloc");
@@ -245,11 +131,6 @@ mdb_status IvfSet::load(mdb_ctx* ctx_, const uint8_t* index, size_t index_len, c
             gather_code_tiles_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, ctx->stream>>>(
                 d_vec.p, d_tsrc.p, d_tlim.p, d_slot_ids.p, pq.m, mw, d_codes.p, total, ctx->d_flags);
     } else {
-        if (quant && quant->dimension && quant->dimension != num_features)
-            return mdb_fail(ctx, MDB_ERR_FORMAT, "quantizer dimension != num_features");
-        if (quantized_dimension != num_features) return mdb_fail(ctx, MDB_ERR_FORMAT, "NoQuantizer: quantized_dimension != num_features");
-        for (auto& o : offsets)
-            if ((o.second + 8) % 4 != 0) return mdb_fail(ctx, MDB_ERR_FORMAT, "f32 vector file is not 4-byte aligned");
         int d4 = ((int)num_features + 3) / 4;
         size_t total4 = ntiles * MDB_UNIT * (size_t)d4;
         MDB_TRY(up32(d_udesc, unit_desc));

@@ -47,7 +47,6 @@ __global__ __launch_bounds__(256) void gather_f32_tiles_kernel(const uint8_t* __
 // list pads to 16 slots, not 64.  (MuopDB's SPANN lists average ~64 vectors — C4: 64.25 — so half of them used to spill one or two
 // vectors into a second 64-slot tile: 1.56 x the rows resident; in units of 16: 1.13 x.  Capacity only: idle lanes never loaded anything.)
 // unit_desc[u] = (first unit of the tile << 4) | (u's position in the tile) << 2 | (units of a narrow tail tile, 0 = a whole tile).
-#define MDB_UPT (MDB_TILE / MDB_UNIT)   // units per whole tile
 __global__ __launch_bounds__(256) void gather_f32_units_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ unit_src,
                                                                const uint32_t* __restrict__ unit_limit, const uint32_t* __restrict__ ids,
                                                                const uint32_t* __restrict__ unit_desc, int d, int d4,

@@ -411,19 +411,23 @@ mdb_status mdb_spann_load(mdb_ctx* ctx, const void* hnsw_index, size_t hnsw_inde
     if (!ctx || !hnsw_index || !hnsw_vectors || !ivf_index || !ivf_vectors || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
     MDB_ENTER(ctx);
+    // the host half of both indexes first (spann_plan_files, mdb_files.cpp): nothing is uploaded for a pair one of whose files is refused
+    IvfPlan iplan;
+    HnswPlan hplan;
+    {
+        std::string why;
+        const mdb_status ps = spann_plan_files({{hnsw_index_offset, hnsw_vectors_offset}}, {{ivf_index_offset, ivf_vectors_offset}}, nullptr,
+                                               (const uint8_t*)hnsw_index, hnsw_index_len, (const uint8_t*)hnsw_vectors, hnsw_vectors_len,
+                                               (const uint8_t*)ivf_index, ivf_index_len, (const uint8_t*)ivf_vectors, ivf_vectors_len, quant, 0, 1,
+                                               IvfSet::plan_opts(ctx), HnswSet::plan_opts(ctx), iplan, hplan, why);
+        if (ps != MDB_OK) return mdb_fail(ctx, ps, "%s", why.c_str());
+    }
     mdb_spann* sp = new mdb_spann();
     sp->set.ctx = ctx;
     sp->set.ivf.coarse_by_scan = false;
-    mdb_status st = sp->set.ivf.load(ctx, (const uint8_t*)ivf_index, ivf_index_len, (const uint8_t*)ivf_vectors, ivf_vectors_len,
-                                     {{ivf_index_offset, ivf_vectors_offset}}, quant, 0, 1);
-    if (st == MDB_OK) {
-        mdb_quant_desc noq{};  // the centroid index is always NoQuantizer<L2> (spann/index.rs:19)
-        noq.kind = MDB_QUANT_NONE;
-        noq.metric = MDB_METRIC_L2;
-        noq.dimension = sp->set.ivf.num_features;
-        st = sp->set.hnsw.load(ctx, (const uint8_t*)hnsw_index, hnsw_index_len, (const uint8_t*)hnsw_vectors, hnsw_vectors_len,
-                               {{hnsw_index_offset, hnsw_vectors_offset}}, &noq, sp->set.ivf.num_features);
-    }
+    mdb_status st = sp->set.ivf.upload(ctx, iplan, (const uint8_t*)ivf_index, ivf_index_len, (const uint8_t*)ivf_vectors, ivf_vectors_len, quant);
+    if (st == MDB_OK)   // the centroid index is always NoQuantizer<L2> (spann/index.rs:19): no quantizer state to upload
+        st = sp->set.hnsw.upload(ctx, hplan, (const uint8_t*)hnsw_index, hnsw_index_len, (const uint8_t*)hnsw_vectors, hnsw_vectors_len, nullptr);
     if (st != MDB_OK) { delete sp; return st; }
     sp->set.num_users = 1;
     mdb_ctx_retain(ctx);
@@ -537,28 +541,25 @@ mdb_status mdb_multi_spann_load(mdb_ctx* ctx, const mdb_user_index_info* users, 
     if (!ctx || (!users && n_users) || !hnsw_index || !hnsw_vectors || !ivf_index || !ivf_vectors || !out) return MDB_ERR_INVALID_ARG;
     *out = nullptr;
     MDB_ENTER(ctx);
-    if (n_users == 0) return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "no users");
+    // the host half of every user's two indexes first (spann_plan_files, mdb_files.cpp): nothing is uploaded for a collection one of
+    // whose blobs is refused
+    std::vector<std::pair<size_t, size_t>> hoff, ioff;
+    std::string why;
+    IvfPlan iplan;
+    HnswPlan hplan;
+    mdb_status st = multi_spann_offsets(users, n_users, hoff, ioff, why);
+    if (st == MDB_OK)
+        st = spann_plan_files(hoff, ioff, &num_features, (const uint8_t*)hnsw_index, hnsw_index_len, (const uint8_t*)hnsw_vectors,
+                              hnsw_vectors_len, (const uint8_t*)ivf_index, ivf_index_len, (const uint8_t*)ivf_vectors, ivf_vectors_len, quant,
+                              shard_rank, shard_world, IvfSet::plan_opts(ctx), HnswSet::plan_opts(ctx), iplan, hplan, why);
+    if (st != MDB_OK) return mdb_fail(ctx, st, "%s", why.c_str());
     mdb_multi_spann* ms = new mdb_multi_spann();
     ms->set.ctx = ctx;
-    std::vector<std::pair<size_t, size_t>> hoff, ioff;
-    for (size_t i = 0; i < n_users; ++i) {
-        hoff.push_back({(size_t)users[i].centroid_index_offset, (size_t)users[i].centroid_vector_offset});
-        ioff.push_back({(size_t)users[i].ivf_index_offset, (size_t)users[i].ivf_vectors_offset});
-        ms->set.user_index[U128Key{users[i].user_id.lo, users[i].user_id.hi}] = (uint32_t)i;
-    }
+    for (size_t i = 0; i < n_users; ++i) ms->set.user_index[U128Key{users[i].user_id.lo, users[i].user_id.hi}] = (uint32_t)i;
     ms->set.ivf.coarse_by_scan = false;
-    mdb_status st = ms->set.ivf.load(ctx, (const uint8_t*)ivf_index, ivf_index_len, (const uint8_t*)ivf_vectors, ivf_vectors_len, ioff,
-                                     quant, shard_rank, shard_world);
-    if (st == MDB_OK && ms->set.ivf.num_features != num_features)
-        st = mdb_fail(ctx, MDB_ERR_FORMAT, "num_features %u != index header %u", num_features, ms->set.ivf.num_features);
-    if (st == MDB_OK) {
-        mdb_quant_desc noq{};
-        noq.kind = MDB_QUANT_NONE;
-        noq.metric = MDB_METRIC_L2;
-        noq.dimension = num_features;
-        st = ms->set.hnsw.load(ctx, (const uint8_t*)hnsw_index, hnsw_index_len, (const uint8_t*)hnsw_vectors, hnsw_vectors_len, hoff,
-                               &noq, num_features);
-    }
+    st = ms->set.ivf.upload(ctx, iplan, (const uint8_t*)ivf_index, ivf_index_len, (const uint8_t*)ivf_vectors, ivf_vectors_len, quant);
+    if (st == MDB_OK)
+        st = ms->set.hnsw.upload(ctx, hplan, (const uint8_t*)hnsw_index, hnsw_index_len, (const uint8_t*)hnsw_vectors, hnsw_vectors_len, nullptr);
     if (st != MDB_OK) { delete ms; return st; }
     ms->set.num_users = n_users;
     mdb_ctx_retain(ctx);

@@ -638,6 +638,7 @@ struct HnswGraph {
 
     // :527-558
     uint32_t entry_point_top_layer() const {
+        if (num_layers == 0) return 0;   // an empty index has no level_offsets[0] to read (orc_hnsw_header asks on every open)
         if (num_layers == 1) {
             size_t num_points = edge_offsets_len / 8 - 1;
             for (size_t i = 0; i < num_points; ++i)

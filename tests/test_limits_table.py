@@ -50,6 +50,12 @@ def test_documented_numbers_follow_the_sources():
     assert "ef > MDB_MAX_K * 2" in hnsw and "o.num_layers > 255" in hnsw            # the checks the table's ef and layer limits restate
     assert "max_neighbors > 64" in read(CSRC, "mdb_hnsw_build.hip")
     assert "num_bits must be 1..8" in read(CSRC, "mdb_core.hip")
+    # the loaders' own limits are checked by their host half (mdb_files.cpp), with numbers the kernels' file holds equal to its own
+    files, files_h = read(CSRC, "mdb_files.cpp"), read(CSRC, "mdb_files.h")
+    assert define(files_h, "MDB_HNSW_MAX_DEGREE") == stride and define(files_h, "MDB_HNSW_MAX_LAYERS") == 255
+    assert "static_assert(HNSW_MAX_STRIDE == MDB_HNSW_MAX_DEGREE && MDB_HNSW_MAX_LAYERS == 255" in hnsw
+    assert "o.num_layers > MDB_HNSW_MAX_LAYERS" in files and "S0 > MDB_HNSW_MAX_DEGREE || SU > MDB_HNSW_MAX_DEGREE" in files
+    assert 'MDB_ERR_UNSUPPORTED, "PQ codes are u8: num_bits must be 1..8"' in files
     for block, rows in (header_rows(), integration_rows()):
         assert "MDB_MAX_K = %d" % max_k in block and "2 * MDB_MAX_K = %d" % (2 * max_k) in block and "HNSW_MAX_STRIDE = %d" % stride in block
         for entry in ("mdb_flat_search", "mdb_ivf_search,", "mdb_hnsw_ann_search"):
