@@ -331,6 +331,14 @@ void mdb_hnsw_free(mdb_hnsw* hnsw);
  * device memory is released when the last handle over it is freed, in any order. */
 mdb_status mdb_hnsw_attach(mdb_ctx* ctx, mdb_hnsw* src, mdb_hnsw** out);
 size_t mdb_hnsw_num_vectors(const mdb_hnsw* hnsw);
+/* What a search of b queries with (k, ef) would launch under the context's CURRENT options, as text; launches nothing.  First a line
+ * `shape key=value ...` (what the dispatch reads of the handle), then one launch per line in launch order:
+ * `role kernel_key gx,gy block lds` — role: pq_quantize | pq_rows | table | top | layer1 | fallback | layer0 | closure; kernel_key: the
+ * kernel's name with its template arguments, `hnsw_beam_kernel<0, true, 8, true, true, 5>`; grid in blocks, block in threads, dynamic
+ * LDS in bytes.  Queries are taken as host rows (mdb_hnsw_ann_search with MDB_MEM_HOST); per_query_users != 0: as a multi-user
+ * caller's (SPANN) would arrive.  The text is cut to len - 1 characters; MDB_ERR_UNSUPPORTED where the search itself refuses ef.
+ * The one function that decides all of this is hnsw_route (csrc/mdb_hnsw_route.h). */
+mdb_status mdb_hnsw_describe_search(mdb_hnsw* hnsw, size_t b, size_t k, uint32_t ef, int per_query_users, char* buf, size_t len);
 /* asynchronous host-buffer form of mdb_hnsw_ann_search (see mdb_ivf_search_submit / mdb_wait) */
 mdb_status mdb_hnsw_ann_search_submit(mdb_hnsw* hnsw, const float* queries, size_t b, size_t k, uint32_t ef, mdb_u128* doc_ids_out,
                                       float* scores_out, uint32_t* counts_out);

@@ -13,12 +13,11 @@
 
 #include "../../include/muopdb_hip.h"
 #include "mdb_arena.h"
-#include "mdb_files.h"   // MDB_TILE / MDB_UNIT, the byte readers, ef_header_error and the loaders' host halves
+#include "mdb_files.h"   // MDB_TILE / MDB_UNIT / MDB_MAX_K, DistPlan, the byte readers, ef_header_error and the loaders' host halves
 
 #define MDB_WAVE 64
 #define MDB_BLOCK 256        // threads per scan block (4 tiles per round)
 #define MDB_KEY_MAX 0xFFFFFFFFFFFFFFFFull
-#define MDB_MAX_K 2048       // largest top-k / ef served by the on-chip selectors
 #define MDB_METRIC_L2SQ 2     // internal: L2 cascade WITHOUT the final sqrt (L2DistanceCalculator::calculate_squared)
 
 
@@ -260,39 +259,6 @@ struct DevBuf {
         return hipMalloc((void**)&p, count * sizeof(T));
     }
 };
-
-// ------------------------------------------------------------------------------------------
-// exact-association distance plan (host computed, passed by value to kernels)
-//   L2  : rs/utils/src/distance/l2.rs:32-67   passes where len/16>0, len/8>0, len/4>0, tail
-//   dot : rs/utils/src/distance/dot_product.rs:38-71  passes where len>16, len>8, len>4, tail
-// all pass offsets are multiples of 4, so every chunk is a whole number of float4s.
-// ------------------------------------------------------------------------------------------
-struct DistPlan {
-    int d;            // true dimension
-    int d4;           // float4s per vector (ceil(d/4))
-    int n16, n8, n4;  // chunks per pass
-    int off8, off4, offt;  // element offsets of the 8-pass, 4-pass and scalar tail
-    int ntail;
-};
-
-inline DistPlan make_plan(int d, int metric) {
-    DistPlan p{};
-    p.d = d;
-    p.d4 = (d + 3) / 4;
-    int rem = d, off = 0;
-    if (metric != MDB_METRIC_DOT) {
-        p.n16 = rem / 16; off += p.n16 * 16; rem -= p.n16 * 16;
-        p.off8 = off; p.n8 = rem / 8; off += p.n8 * 8; rem -= p.n8 * 8;
-        p.off4 = off; p.n4 = rem / 4; off += p.n4 * 4; rem -= p.n4 * 4;
-    } else {
-        p.n16 = rem > 16 ? rem / 16 : 0; off += p.n16 * 16; rem -= p.n16 * 16;
-        p.off8 = off; p.n8 = rem > 8 ? rem / 8 : 0; off += p.n8 * 8; rem -= p.n8 * 8;
-        p.off4 = off; p.n4 = rem > 4 ? rem / 4 : 0; off += p.n4 * 4; rem -= p.n4 * 4;
-    }
-    p.offt = off;
-    p.ntail = rem;
-    return p;
-}
 
 // device-resident list-contiguous SoA store of f32 vectors:
 //   float4 index of (vector v, float4 c4) = ((v / 64) * d4 + c4) * 64 + (v % 64)

@@ -3,6 +3,7 @@
 #include <cstdarg>
 
 #include "mdb_device.hip.h"
+#include "mdb_hnsw_route.h"
 #include "mdb_kernels.h"
 #include "mdb_launch.hip.h"
 
@@ -451,7 +452,6 @@ __global__ __launch_bounds__(256) void pq_quantize_kernel(const float* __restric
 
 // K = 256, subdim = 8: a wave keeps its subspace's rows in registers for PQ8_VQ vectors (one wave per (vector, subspace) re-read the
 // 8 KB slice of the codebook from L2 for every vector: 512 MB of L2 traffic for 4096 queries x 16 subspaces — 31 us at C5)
-#define PQ8_VQ 8
 __global__ __launch_bounds__(256) void pq_quantize8_kernel(const float* __restrict__ vecs, size_t n, int row_stride, int m,
                                                            const float* __restrict__ cb, uint8_t* __restrict__ codes) {
     const int lane = threadIdx.x & 63, s = blockIdx.y;
@@ -470,17 +470,16 @@ __global__ __launch_bounds__(256) void pq_quantize8_kernel(const float* __restri
 
 mdb_status pq_quantize_device(mdb_ctx* ctx, const PqDev& pq, const float* d_vecs, size_t n, uint8_t* d_codes, int row_stride) {
     if (n == 0) return MDB_OK;
-    DistPlan sp = make_plan(pq.subdim, MDB_METRIC_L2);  // quantize always uses squared L2 (pq/mod.rs:167)
-    size_t total = n * (size_t)pq.m;
-    if (pq.K == 256 && pq.subdim == 8 && !ctx->opt.pq_no_quantize8) {
-        const size_t groups = (n + PQ8_VQ - 1) / PQ8_VQ;
-        pq_quantize8_kernel<<<dim3((unsigned)((groups + 3) / 4), (unsigned)pq.m), 256, 0, ctx->stream>>>(d_vecs, n, row_stride ? row_stride : pq.dimension,
-                                                                                                  pq.m, pq.codebook.p, d_codes);
-        MDB_HIP(ctx, hipGetLastError());
-        return MDB_OK;
+    HnswRoute r;   // the form and its grid: pq_quantize_route (mdb_hnsw_route.h), shared with the HNSW route
+    pq_quantize_route(r, pq.m, pq.K, pq.subdim, n, ctx->opt.pq_no_quantize8 != 0);
+    const HnswLaunch& l = r.launch[0];
+    if (l.kernel == HK_PQ_QUANTIZE8) {
+        pq_quantize8_kernel<<<dim3(l.gx, l.gy), l.block, 0, ctx->stream>>>(d_vecs, n, row_stride ? row_stride : pq.dimension, pq.m, pq.codebook.p, d_codes);
+    } else {
+        const DistPlan sp = make_plan(pq.subdim, MDB_METRIC_L2);  // quantize always uses squared L2 (pq/mod.rs:167)
+        pq_quantize_kernel<<<dim3(l.gx), l.block, 0, ctx->stream>>>(d_vecs, n, row_stride ? row_stride : pq.dimension, pq.subdim, pq.m, pq.K,
+                                                                   pq.codebook.p, sp, d_codes);
     }
-    pq_quantize_kernel<<<dim3((unsigned)((total + 3) / 4)), 256, 0, ctx->stream>>>(d_vecs, n, row_stride ? row_stride : pq.dimension, pq.subdim, pq.m,
-                                                                                   pq.K, pq.codebook.p, sp, d_codes);
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
 }

@@ -18,6 +18,40 @@
 #define MDB_UPT (MDB_TILE / MDB_UNIT)   // units per whole tile
 #define MDB_HNSW_MAX_DEGREE 256  // largest node degree a graph may have: HNSW_MAX_STRIDE of mdb_hnsw.hip (static_assert there)
 #define MDB_HNSW_MAX_LAYERS 255  // levels are u8 on the device (HnswSet::d_level)
+#define MDB_MAX_K 2048       // largest top-k / ef served by the on-chip selectors
+
+// ------------------------------------------------------------------------------------------
+// exact-association distance plan (host computed, passed by value to kernels)
+//   L2  : rs/utils/src/distance/l2.rs:32-67   passes where len/16>0, len/8>0, len/4>0, tail
+//   dot : rs/utils/src/distance/dot_product.rs:38-71  passes where len>16, len>8, len>4, tail
+// all pass offsets are multiples of 4, so every chunk is a whole number of float4s.
+// ------------------------------------------------------------------------------------------
+struct DistPlan {
+    int d;            // true dimension
+    int d4;           // float4s per vector (ceil(d/4))
+    int n16, n8, n4;  // chunks per pass
+    int off8, off4, offt;  // element offsets of the 8-pass, 4-pass and scalar tail
+    int ntail;
+};
+
+inline DistPlan make_plan(int d, int metric) {
+    DistPlan p{};
+    p.d = d;
+    p.d4 = (d + 3) / 4;
+    int rem = d, off = 0;
+    if (metric != MDB_METRIC_DOT) {
+        p.n16 = rem / 16; off += p.n16 * 16; rem -= p.n16 * 16;
+        p.off8 = off; p.n8 = rem / 8; off += p.n8 * 8; rem -= p.n8 * 8;
+        p.off4 = off; p.n4 = rem / 4; off += p.n4 * 4; rem -= p.n4 * 4;
+    } else {
+        p.n16 = rem > 16 ? rem / 16 : 0; off += p.n16 * 16; rem -= p.n16 * 16;
+        p.off8 = off; p.n8 = rem > 8 ? rem / 8 : 0; off += p.n8 * 8; rem -= p.n8 * 8;
+        p.off4 = off; p.n4 = rem > 4 ? rem / 4 : 0; off += p.n4 * 4; rem -= p.n4 * 4;
+    }
+    p.offt = off;
+    p.ntail = rem;
+    return p;
+}
 
 // host-side byte readers (little-endian files)
 static inline uint32_t rd_u32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }

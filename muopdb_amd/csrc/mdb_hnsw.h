@@ -3,6 +3,7 @@
 #include <utility>
 
 #include "mdb_common.h"
+#include "mdb_hnsw_route.h"
 
 // SPANN: the ratio filter of Spann::search (rs/index/src/spann/index.rs:229-246) applied by the centroid-graph launch itself, in the tail of
 // hnsw_closure_kernel (no launch of its own: 5 us + a gap of a 120 us step).  probes == nullptr: no filter.  done: set by HnswSet::search
@@ -52,22 +53,12 @@ struct HnswUpperOut {
                                    // it from the top with the general traversal, which counts everything itself)
     uint32_t words = 0;
 };
-// table[q][c] = order-preserving image of distance(query q, compact point c), exact association (mdb_device.hip.h exact_sums)
-// (zero16 != nullptr: the kernel also clears those 16 counter words — stream order puts that ahead of the traversal kernels)
-mdb_status hnsw_upper_table(mdb_ctx* ctx, const HnswUpper& up, int metric, const DistPlan& p, const float* d_q, int qstride, size_t b,
-                            uint32_t* d_table, unsigned long long* zero16 = nullptr);
-// layers num_layers-1 .. 1 of ann_search on the table; fills `out`, adds the layers' evaluations / expansions to ctx->d_counters
-mdb_status hnsw_upper_traverse(mdb_ctx* ctx, const HnswUpper& up, const uint32_t* d_table, size_t b, uint32_t ef, const HnswUpperOut& out);
-// table + traversal in the shape that suits the batch: hnsw_upper_table then hnsw_upper_traverse, or — batches of >= 32 queries over a
-// graph of >= 3 layers — the split path (mdb_hnsw_upper.hip: top layers and the table pass in one launch, then layer 1).
-// d_table: b * nu_pad words; d_state: (b * (words + 8) + 64) words of scratch for the hand-over between the two launches.
-// table path: the beam on four registers of 64 slots when ef leaves them MDB_HNSW_NB4_SLACK free slots (256 - ef: the accepted
-// neighbours between two compactions, and the exact ties with furthest a query may hold before it is re-run by the general kernel)
-static inline bool hnsw_beam_nb4(const mdb_ctx* ctx, uint32_t ef) {
-    return ctx->opt.hnsw_nb4_slack > 0 && (long long)ef + ctx->opt.hnsw_nb4_slack <= 256;
-}
-mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const DistPlan& p, const float* d_q, int qstride, size_t b,
-                          uint32_t ef, uint32_t* d_table, uint32_t* d_state, const HnswUpperOut& out, unsigned long long* zero16);
+// the upper layers of a call on the table path, as its route (mdb_hnsw_route.h) lists them: the table / top / layer1 / fallback launches.
+// table[q][c] = order-preserving image of distance(query q, compact point c), exact association (mdb_device.hip.h exact_sums).
+// d_table: route.table_bytes, d_state: route.hand_bytes of scratch (the hand-over between the launches and the fb words); fills `out`.
+// zero16 != nullptr: the first launch also clears those 16 counter words — stream order puts that ahead of the traversal kernels
+mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, const DistPlan& p, const float* d_q, int qstride, size_t b,
+                          const HnswRoute& route, uint32_t* d_table, uint32_t* d_state, const HnswUpperOut& out, unsigned long long* zero16);
 
 // device-resident calls: where the layer-0 kernel may write the caller's (doc id, score) rows itself; done = it did
 struct HnswRemapOut {
@@ -121,6 +112,26 @@ struct HnswSet {
         po.no_dense = c->opt.hnsw_no_dense != 0;
         po.no_table = c->opt.hnsw_no_table != 0;
         return po;
+    }
+    // what hnsw_route (mdb_hnsw_route.h) reads of the context's options and of this set
+    static HnswRouteOpts route_opts(const mdb_ctx* c) {
+        HnswRouteOpts ro;
+#define X(field, dflt)                                                                                             \
+    static_assert(mdb_options{}.field == dflt, "mdb_hnsw_route.h states another default than MDB_OPTIONS"); \
+    ro.field = c->opt.field;
+        HNSW_ROUTE_OPTS(X)
+#undef X
+        return ro;
+    }
+    HnswShape shape() const {
+        HnswShape s;
+        s.kind = kind; s.metric = metric; s.dimension = dimension; s.dpad = dpad;
+        s.max_n = max_n; s.max_stride = max_stride; s.max_rows0 = max_rows0; s.max_rowsU = max_rowsU; s.all_dense = all_dense;
+        s.pq_m = pq.m; s.pq_K = pq.K; s.pq_subdim = pq.subdim;
+        s.nu = upper.nu; s.nu2 = upper.nu2; s.su = upper.su; s.layers = upper.layers; s.small_layer = upper.small_layer;
+        s.ntiles = upper.tiles.ntiles; s.ntiles2 = upper.tiles2.ntiles;
+        s.rows_nat = upper.rows_nat.p != nullptr; s.map21 = upper.map21.p != nullptr;
+        return s;
     }
     // beam search of every query through its user's graph: device keys [b][k] (distance, point id)
     // ascending + counts.  d_q_user == nullptr => user 0.

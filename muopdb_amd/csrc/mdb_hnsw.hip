@@ -28,8 +28,7 @@
 #include "mdb_kernels.h"
 #include "mdb_launch.hip.h"
 
-#define HNSW_BLOCK 256
-#define HNSW_MAX_STRIDE 256
+#define HNSW_MAX_STRIDE 256   // (HNSW_BLOCK, beam_block and the beam kernel's LDS layout sizes: mdb_hnsw_route.h)
 // what the kernels below are sized for is what the loader's host half (hnsw_plan_files, mdb_files.cpp) holds a file to: it refuses a
 // node degree above MDB_HNSW_MAX_DEGREE and `o.num_layers > 255` (MDB_HNSW_MAX_LAYERS) with MDB_ERR_UNSUPPORTED
 static_assert(HNSW_MAX_STRIDE == MDB_HNSW_MAX_DEGREE && MDB_HNSW_MAX_LAYERS == 255, "the host half checks other limits than the kernels have");
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(HNSW_BLOCK) void hnsw_search_kernel(HnswArgs a) {
 // front (ceil(n / groups) passes whose loads are all in flight: the same group16 distance, the same bits; a point the closure never
 // reaches is never looked at again, so rows and counters are unchanged) and copies the rows next to them; a round is then LDS reads,
 // LDS atomics and one barrier.
-struct ClosureStage { uint32_t dtab_off, rows0_off, rowsU_off; };
+// (ClosureStage: mdb_hnsw_route.h, where hnsw_route lays the staging out)
 template <int METRIC, int N16T, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void hnsw_closure_kernel(HnswArgs a, int wcap, ClosureStage st, ClosureFilter cf) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -738,17 +737,12 @@ __global__ __launch_bounds__(BLOCK) void hnsw_closure_kernel(HnswArgs a, int wca
 // distance waves (28 groups): by a CPU estimate on a 100 k k-NN graph 99.8 % of its steps bring at most 28 new neighbours (23 % bring
 // more than the 12 that three waves hold) and then take the one-vector-per-group path whose gather is requested right behind the barrier, in a single pass.  The CU holds
 // one block either way (LDS), so the extra waves take slots nobody uses.
-#ifndef MDB_HNSW_L0_BLOCK
-#define MDB_HNSW_L0_BLOCK 512
-#endif
+// (MDB_HNSW_L0_BLOCK = 512: mdb_hnsw_route.h)
 // MDB_HNSW_L0_IDLE4: wave 4 — the one that shares wave 0's SIMD — only attends the barriers (six distance waves, 24 groups)
 #ifndef MDB_HNSW_L0_IDLE4
 #define MDB_HNSW_L0_IDLE4 0
 #endif
-__host__ __device__ constexpr int beam_block(bool l0) { return l0 ? MDB_HNSW_L0_BLOCK : HNSW_BLOCK; }
-// W (the sorted working set of the result: 64 NB keys rounded to 2 / 4 KB) | C 1024 keys | nb_id | nb_dist | misc | qs | vis
-__host__ __device__ constexpr int beam_lds_c(int nb) { return nb <= 5 ? 2048 : 4096; }
-__host__ __device__ constexpr int beam_lds_qs(int nb) { return beam_lds_c(nb) + 8192 + 1024 + 1024 + 64; }
+// (beam_block, beam_lds_c, beam_lds_qs: mdb_hnsw_route.h)
 
 // ROW64: every adjacency row of the index has at most 64 edges (max_neighbors <= 32: the configurations' graphs) — a row is ONE
 // register per lane, a step has ONE chunk: the per-chunk loops, their scalar branches and three of four register copies leave
@@ -1462,145 +1456,94 @@ mdb_status HnswSet::upload(mdb_ctx* ctx_, const HnswPlan& plan, const uint8_t* i
 }
 
 // ------------------------------------------------------------------------------------------ search
+// Executes the call's route (hnsw_route, mdb_hnsw_route.h: every choice of kernel form, size and scratch is made there): takes the scratch
+// it sizes, fills the kernels' arguments and walks its launches.
 mdb_status HnswSet::search(const float* d_q, int qstride, size_t b, const uint32_t* d_q_user, size_t k, uint32_t ef,
                            uint64_t* d_keys, uint32_t* d_counts, bool zero_counters, HnswRemapOut* fuse, ClosureFilter* cf) {
     if (fuse) fuse->done = false;
     if (cf) cf->done = false;
     if (b == 0) return MDB_OK;
     ctx->counters_clean = false;   // this writes d_counters[0..3]: whoever relies on "still zero from the last call" (spann_search_impl) re-arms the flag AFTER it
-    if (ef == 0) ef = 1;  // `len < ef` is never true and every push is followed by a pop: same as ef = 1
-    if (ef > MDB_MAX_K * 2) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "ef=%u exceeds %d", ef, MDB_MAX_K * 2);
+    HnswCall call;
+    call.b = b; call.k = k; call.ef = ef; call.qstride = qstride; call.per_query_users = d_q_user != nullptr;
+    call.fuse = fuse && fuse->doc; call.filter = cf && cf->probes;
+    const HnswRoute r = hnsw_route(shape(), call, route_opts(ctx));
+    if (r.status != MDB_OK) return mdb_fail(ctx, r.status, "ef=%u exceeds %d", r.ef, MDB_MAX_K * 2);
     HnswArgs a{};
     a.users = d_users.p; a.q_user = d_q_user; a.adj = d_adj.p; a.upper_first = d_upper_first.p; a.level = d_level.p;
     a.vecs = d_vecs.p; a.q = d_q; a.qstride = qstride; a.dpad = dpad; a.p = make_plan((int)dimension, metric);
+    int li = 0;   // the next launch of the route
     if (kind == MDB_QUANT_PQ) {
         // the query is quantized like a stored point (index.rs:168) and written out as its codebook rows
         void *qcodes, *qrows;
         MDB_TRY(mdb_scratch(ctx, b * (size_t)pq.m + 16, &qcodes));
         MDB_TRY(mdb_scratch(ctx, b * (size_t)qstride * 4 + 16, &qrows));
-        MDB_TRY(pq_quantize_device(ctx, pq, d_q, b, (uint8_t*)qcodes, qstride));
-        size_t tq = b * (size_t)qstride;
-        pq_rows_kernel<<<dim3((unsigned)((tq + 255) / 256)), 256, 0, ctx->stream>>>((const uint8_t*)qcodes, nullptr, (size_t)pq.m, pq.m,
-                                                                                   pq.subdim, pq.K, pq.codebook.p, qstride, (float*)qrows, tq);
+        MDB_TRY(pq_quantize_device(ctx, pq, d_q, b, (uint8_t*)qcodes, qstride));   // HR_PQ_QUANTIZE
+        const HnswLaunch& l = r.launch[1];                                         // HR_PQ_ROWS
+        pq_rows_kernel<<<dim3(l.gx), l.block, 0, ctx->stream>>>((const uint8_t*)qcodes, nullptr, (size_t)pq.m, pq.m, pq.subdim, pq.K,
+                                                                pq.codebook.p, qstride, (float*)qrows, b * (size_t)qstride);
         MDB_HIP(ctx, hipGetLastError());
+        li = 2;
         a.q = (const float*)qrows;
         a.pq_m = pq.m;
         a.pq_subdim = pq.subdim;
         a.sp = make_plan(pq.subdim, MDB_METRIC_L2);
     }
-    a.ef = (int)ef;
-    a.ef_cap = ((int)ef + 63) / 64 * 64;
-    int p2 = 1024;  // sort / staging buffer of the beam kernel (512 keys + 512 flag words) fits as well
-    while (p2 < a.ef_cap + 192) p2 <<= 1;
-    a.cand_cap = p2;  // ring capacity (power of two): live candidates <= ef + ties
-    a.smax = std::max<int>(64, ((int)max_stride + 63) / 64 * 64);
+    a.ef = (int)r.ef; a.ef_cap = r.ef_cap; a.cand_cap = r.cand_cap; a.smax = r.smax;
     a.k = (int)k;
     a.out_keys = d_keys; a.out_counts = d_counts; a.flags = ctx->d_flags; a.counters = ctx->d_counters;
-    size_t lds_base = (size_t)a.ef_cap * 8 + (size_t)a.cand_cap * 8 + (size_t)a.smax * 8 + (size_t)dpad * 4 + 64;
-    if (ef <= 448) lds_base = std::max<size_t>(lds_base, (size_t)beam_lds_qs(ef <= 256 ? 5 : 8) + (size_t)dpad * 4);  // the beam kernel's fixed layout
-    size_t words = ((size_t)max_n + 31) / 32 + 1;
-    bool vis_lds = lds_base + words * 4 <= 160 * 1024 - 256;
-    size_t lds = lds_base + (vis_lds ? words * 4 : 0);
-    a.vis_words = words;
-    if (!vis_lds) {
+    a.vis_words = r.vis_words;
+    if (!r.vis_lds) {
         void* vg;
-        MDB_TRY(mdb_scratch(ctx, b * words * 4, &vg));
-        MDB_HIP(ctx, hipMemsetAsync(vg, 0, b * words * 4, ctx->stream));
+        MDB_TRY(mdb_scratch(ctx, r.vis_bytes, &vg));
+        MDB_HIP(ctx, hipMemsetAsync(vg, 0, r.vis_bytes, ctx->stream));
         a.vis_global = (uint32_t*)vg;
     }
     ProfScope prof(ctx, 2);
-    // specialised distance when the whole vector is 16-lane chunks (d = 128 / 768: the configs' dims)
-    const int nf = (kind != MDB_QUANT_PQ && a.p.n8 == 0 && a.p.n4 == 0 && a.p.ntail == 0 && !ctx->opt.hnsw_generic_dist) ? a.p.n16 : 0;
-    // graphs no larger than ef (SPANN centroid graphs): frontier-parallel closure, see hnsw_closure_kernel
-    if (max_n <= ef && max_n <= 4096 && !ctx->opt.hnsw_no_closure) {
-        if (zero_counters) { ctx->counters_clean = false; MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 128, ctx->stream)); }
-        int wcap = 64;
-        while ((uint32_t)wcap < max_n) wcap <<= 1;
-        // small batches: 64 groups per query (latency); large ones: 256-thread blocks, four resident per CU
-        const bool big = ctx->opt.closure_block > 0 ? ctx->opt.closure_block >= 1024 : b <= 256;
-        size_t clds = (size_t)wcap * 16 + (size_t)dpad * 4 + 8 + 64 + (((size_t)max_n + 31) / 32 + 1) * 4;
-        // staging (ClosureStage): every point's distance up front + the rows in LDS, while the block keeps its residency (one 1024-thread
-        // block per CU: up to 120 KB; four 256-thread blocks per CU: 40 KB each)
-        ClosureFilter cfk;   // the SPANN ratio filter in the kernel's tail (k keys per query fit the frontier words: k <= wcap)
-        if (cf && cf->probes && !ctx->opt.closure_no_filter && k <= (size_t)wcap) { cfk = *cf; cf->done = true; }
-        ClosureStage stg{0u, 0u, 0u};
-        // (only the one-block-per-CU form: with four 256-thread blocks per CU the rounds of one block already hide behind the others',
-        // and the up-front passes cost the full C4 batch of 1024 pairs + 4 %: 0.496 -> 0.517 ms)
-        if (!ctx->opt.closure_no_stage && big) {
-            const size_t budget = 120 * 1024;
-            clds = (clds + 15) & ~(size_t)15;
-            if (clds + (size_t)max_n * 4 + 16 <= budget) {
-                stg.dtab_off = (uint32_t)clds;
-                clds = (clds + (size_t)max_n * 4 + 15) & ~(size_t)15;
-                if (max_rows0 && clds + (size_t)max_rows0 * 4 + 16 <= budget) {
-                    stg.rows0_off = (uint32_t)clds;
-                    clds = (clds + (size_t)max_rows0 * 4 + 15) & ~(size_t)15;
-                }
-                if (max_rowsU && all_dense && clds + (size_t)max_rowsU * 4 + 16 <= budget) {
-                    stg.rowsU_off = (uint32_t)clds;
-                    clds = (clds + (size_t)max_rowsU * 4 + 15) & ~(size_t)15;
-                }
-            }
-        }
-        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-            return mdb_pick<1024, 256>(big ? 1024 : 256, [&](auto CB) {
-                return mdb_pick<8, 48, 0>(nf, [&](auto NF) {
-                    return mdb_launch(ctx, hnsw_closure_kernel<M(), NF(), CB()>, dim3((unsigned)b), CB(), clds, a, wcap, stg, cfk);
-                });
-            });
-        }));
-        MDB_HIP(ctx, hipGetLastError());
-        return MDB_OK;
-    }
-    // ef <= 256: register-resident beam; above: sorted LDS sets (MDB_HNSW_NO_BEAM forces the latter, for tests)
-    const bool beam = ef <= 256 && !ctx->opt.hnsw_no_beam;
-    // the table path's kernels exist with an 8-register beam as well (512 slots): ef up to 448 (SearchParams.ef_construction is the
-    // caller's, rs/config/src/search_params.rs:1-34) stays off the general kernel, which is 3x slower per expansion
-    const bool beam_wide = ef > 256 && ef <= 448 && !ctx->opt.hnsw_no_beam && !ctx->opt.hnsw_no_wide;
-    const bool row64 = max_stride <= 64 && !ctx->opt.hnsw_no_row64;   // hnsw_beam_kernel's one-chunk specialisation
-    // upper layers on the distance table (mdb_hnsw_upper.hip): table pass, single-wave traversal, then the layer-0 instance of
-    // the beam kernel.  One graph (no per-query user), f32 rows; the table is b * nu words of scratch
-    const uint32_t nu_pad = (uint32_t)upper.tiles.ntiles * MDB_TILE;
-    const bool table = upper.nu > 0 && !d_q_user && (beam || beam_wide) && row64 && kind != MDB_QUANT_PQ && !ctx->opt.hnsw_no_table &&
-                       (long long)b >= ctx->opt.hnsw_table_min_b && (uint64_t)b * nu_pad * 4 <= ((uint64_t)2 << 30) &&
-                       (size_t)(upper.nu / 32 + 4) * 4 <= 96 * 1024;
-    if (table) {
-        const uint32_t words = (upper.nu / 32 + 4) & ~3u;   // a multiple of 4: hnsw_upper_kernel puts the table row's LDS copy (16-byte stores) behind the bitmap
-        void *tab, *st;
-        MDB_TRY(mdb_scratch(ctx, (size_t)b * nu_pad * 4 + 64, &tab));
-        MDB_TRY(mdb_scratch(ctx, (size_t)b * (words + 6) * 4 + 64, &st));
-        void* st2;
-        MDB_TRY(mdb_scratch(ctx, ((size_t)b * (words + 8) + 64) * 4, &st2));
+    ClosureFilter cfk;   // hnsw_closure_kernel's tail
+    if (r.cf_done) { cfk = *cf; cf->done = true; }
+    if (r.table) {
+        void *tab, *st, *st2;
+        MDB_TRY(mdb_scratch(ctx, r.table_bytes, &tab));
+        MDB_TRY(mdb_scratch(ctx, r.out_bytes, &st));
+        MDB_TRY(mdb_scratch(ctx, r.hand_bytes, &st2));
         HnswUpperOut uo;
         uo.ep = (uint32_t*)st;
-        uo.ovf = uo.ep + b;
-        uo.cnt = uo.ovf + b;
-        uo.vis = uo.cnt + 4 * b;
-        uo.words = words;
-        // (the table kernel clears the context's traversal counters on its way: no memset launch in front of the step)
-        MDB_TRY(hnsw_upper_run(ctx, upper, metric, a.p, d_q, qstride, b, ef, (uint32_t*)tab, (uint32_t*)st2, uo,
+        uo.ovf = uo.ep + r.st_ovf;
+        uo.cnt = uo.ep + r.st_cnt;
+        uo.vis = uo.ep + r.st_vis;
+        uo.words = r.up_words;
+        // (the first upper launch clears the context's traversal counters on its way: no memset launch in front of the step)
+        MDB_TRY(hnsw_upper_run(ctx, upper, a.p, d_q, qstride, b, r, (uint32_t*)tab, (uint32_t*)st2, uo,
                                zero_counters ? ctx->d_counters : nullptr));
         zero_counters = false;
-        a.up_ep = uo.ep; a.up_ovf = uo.ovf; a.up_vis = uo.vis; a.up_cnt = uo.cnt; a.up_ids = upper.ids.p; a.up_words = words;
-        if (fuse && fuse->doc && k > 0) {
+        li = r.n - 1;
+        a.up_ep = uo.ep; a.up_ovf = uo.ovf; a.up_vis = uo.vis; a.up_cnt = uo.cnt; a.up_ids = upper.ids.p; a.up_words = r.up_words;
+        if (r.fuse_done) {
             a.rm_index = d_index.p; a.rm_doc = fuse->doc; a.rm_score = fuse->score; a.rm_counts = fuse->counts;
             fuse->done = true;
         }
     }
     if (zero_counters) { ctx->counters_clean = false; MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 128, ctx->stream)); }
-    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-        return mdb_pick_bool(vis_lds, [&](auto VL) {
-            return mdb_pick<8, 48, 0>(nf, [&](auto NF) {
-                const dim3 grid((unsigned)b);
-                if (table)   // layer 0 behind the table pass: the beam's registers as in upper_launch_bottom
-                    return mdb_pick<4, 5, 8>(hnsw_beam_nb4(ctx, ef) ? 4 : ef <= 256 ? 5 : 8, [&](auto NB) {
-                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), true, true, NB()>, grid, beam_block(true), lds, a);
+    const HnswLaunch& l = r.launch[li];   // HR_CLOSURE or HR_LAYER0: the last launch
+    const dim3 grid(l.gx);
+    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(l.targ[0], [&](auto M) {
+        if (l.kernel == HK_CLOSURE)
+            return mdb_pick<1024, 256>(l.targ[2], [&](auto CB) {
+                return mdb_pick<8, 48, 0>(l.targ[1], [&](auto NF) {
+                    return mdb_launch(ctx, hnsw_closure_kernel<M(), NF(), CB()>, grid, l.block, l.lds, a, r.wcap, r.stage, cfk);
+                });
+            });
+        return mdb_pick_bool(l.targ[1] != 0, [&](auto VL) {
+            return mdb_pick<8, 48, 0>(l.targ[2], [&](auto NF) {
+                if (l.kernel == HK_SEARCH) return mdb_launch(ctx, hnsw_search_kernel<M(), VL(), NF()>, grid, l.block, l.lds, a);
+                if (l.targ[4])   // layer 0 behind the table path
+                    return mdb_pick<4, 5, 8>(l.targ[5], [&](auto NB) {
+                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), true, true, NB()>, grid, l.block, l.lds, a);
                     });
-                if (beam)
-                    return mdb_pick_bool(row64, [&](auto R64) {
-                        return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), R64()>, grid, HNSW_BLOCK, lds, a);
-                    });
-                return mdb_launch(ctx, hnsw_search_kernel<M(), VL(), NF()>, grid, HNSW_BLOCK, lds, a);
+                return mdb_pick_bool(l.targ[3] != 0, [&](auto R64) {
+                    return mdb_launch(ctx, hnsw_beam_kernel<M(), VL(), NF(), R64()>, grid, l.block, l.lds, a);
+                });
             });
         });
     }));
@@ -1685,6 +1628,25 @@ mdb_status mdb_hnsw_attach(mdb_ctx* ctx, mdb_hnsw* src, mdb_hnsw** out) {
 }
 
 size_t mdb_hnsw_num_vectors(const mdb_hnsw* h) { return h ? (size_t)h->set.blobs[0].num_vectors : 0; }
+
+mdb_status mdb_hnsw_describe_search(mdb_hnsw* h, size_t b, size_t k, uint32_t ef, int per_query_users, char* buf, size_t len) {
+    if (!h || !buf || !len) return MDB_ERR_INVALID_ARG;
+    buf[0] = 0;
+    const HnswSet& s = h->set;
+    mdb_ctx* ctx = s.ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);   // the options are read under the context's lock; no device call, no scratch
+    HnswCall call;
+    call.b = b; call.k = k; call.ef = ef; call.per_query_users = per_query_users != 0;
+    call.qstride = ((int)s.dimension + 3) / 4 * 4 + 16;   // stage_queries' rows
+    const HnswShape shape = s.shape();
+    const HnswRoute r = hnsw_route(shape, call, HnswSet::route_opts(ctx));
+    if (r.status != MDB_OK) return mdb_fail(ctx, r.status, "ef=%u exceeds %d", r.ef, MDB_MAX_K * 2);
+    size_t w = (size_t)snprintf(buf, len, "shape ");
+    if (w < len) w += hnsw_shape_text(shape, buf + w, len - w);
+    if (w < len) w += (size_t)snprintf(buf + w, len - w, "\n");
+    if (w < len) hnsw_route_text(r, buf + w, len - w);
+    return MDB_OK;
+}
 
 static mdb_status hnsw_ann_search_impl(mdb_hnsw* h, const float* queries, size_t b, size_t k, uint32_t ef, mdb_mem mem,
                                        mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out, bool submit);

@@ -40,8 +40,7 @@
 // HnswUpArgs::fb_role, so the launch shape, the table blocks and the kernel inventory stay what they were.
 #pragma once
 
-#define CL_FR_CAP 512u           // a frontier list: certain points are fewer than ef <= 448; theta = +inf only over <= max(ef, 64) points
-#define CL_SUBHIST 4             // histograms of the select (waves spread over them)
+// (CL_FR_CAP, CL_SUBHIST, CL_SH_WORDS and cl_lds_words: mdb_hnsw_route.h)
 // shared words of the block
 #define CL_SH_NNEXT 0            // [2] length of the next frontier, by round parity
 #define CL_SH_EVALS 2
@@ -56,13 +55,9 @@
 #define CL_SH_MINU 12            // u64: min (image, ~id) over evaluated and unexpanded
 #define CL_SH_MINE 14            // u64: min (image, id) over evaluated
 #define CL_SH_FLAGGED 16         // how closure_traverse ended, for its caller
-#define CL_SH_WORDS 32
 struct ClLds {
     uint32_t *sh, *hist, *fr, *vis, *ev, *ex, *vis_out, *row;
 };
-__host__ __device__ inline size_t cl_lds_words(uint32_t vis_words, uint32_t out_words, uint32_t row_words) {
-    return (size_t)CL_SH_WORDS + CL_SUBHIST * 256 + 2 * CL_FR_CAP + 3 * (size_t)vis_words + out_words + row_words;
-}
 // (every part a multiple of four words: the row's copy is written with 16-byte stores)
 __device__ __forceinline__ ClLds cl_carve(uint32_t* p, uint32_t vis_words, uint32_t out_words) {
     ClLds L;

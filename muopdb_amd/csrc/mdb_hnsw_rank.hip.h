@@ -19,7 +19,7 @@
 
 #define RK_NONE 0xFFFFFFFFu
 #define RK_NAN_KEY 0xFFFFFFFEu
-#define RK_MAX_POINTS 32768u       // 15-bit ranks / compact indices + the tie flag in one u16
+// (RK_MAX_POINTS = 32768, RK_BLOCK, RK_HIST_WORDS and rk_lds_bytes: mdb_hnsw_route.h)
 
 template <int NW> struct BmVec { typedef uint32_t type __attribute__((ext_vector_type(NW))); };
 template <> struct BmVec<1> { typedef uint32_t type; };
@@ -750,15 +750,11 @@ __device__ __forceinline__ void upper_traverse_rank1(const HnswUpArgs& a, const 
     }
 }
 
-// LDS of the rank kernels behind the visited bitmap: two u16 arrays of nu_pad (P, R), the sort's histograms, a few words
-#define RK_HIST_WORDS(NT) ((NT) / 64 * 256)
-__host__ __device__ inline size_t rk_lds_bytes(uint32_t vis_words, uint32_t nu_pad, int nt, uint32_t extra_words) {
-    return UP_LDS_VIS + (size_t)vis_words * 4 + (size_t)nu_pad * 4 + (size_t)RK_HIST_WORDS(nt) * 4 + 64 * 4 + (size_t)extra_words * 4;
-}
+// LDS of the rank kernels behind the visited bitmap (rk_lds_bytes, mdb_hnsw_route.h): two u16 arrays of nu_pad (P, R), the sort's
+// histograms, a few words
 
 // layers a.layer_hi .. a.layer_lo on the table rows of an earlier launch: sort the query's row, traverse — or, when the launch runs
-// the frontier form (a.fb_role CL_ROLE_BOTTOM / CL_ROLE_SINGLE), the block of mdb_hnsw_closure.hip.h, which wants these 1024 threads
-#define RK_BLOCK 1024
+// the frontier form (a.fb_role CL_ROLE_BOTTOM / CL_ROLE_SINGLE), the block of mdb_hnsw_closure.hip.h, which wants these RK_BLOCK = 1024 threads
 template <int NT> __device__ void closure_bottom_block(const HnswUpArgs& a);
 template <int NW>
 __global__ __launch_bounds__(RK_BLOCK) void hnsw_upper_rank_kernel(HnswUpArgs a) {

@@ -147,7 +147,7 @@ struct T64Point<METRIC, N16, N16> {
     static __device__ __forceinline__ void run(float (&)[16], const float (&)[N16], const float (&)[16 * N16]) {}
 };
 
-#define T64_PPW 16   // points per wave
+// (T64_PPW points per wave: mdb_hnsw_route.h)
 // (a block of 256 threads; bx = its slice of the points, by = its group of 64 queries)
 template <int METRIC, int N16>
 __device__ __forceinline__ void table64_block(const float* __restrict__ rows, uint32_t nu, const float* __restrict__ q, int qstride, uint32_t b,
@@ -208,54 +208,6 @@ __global__ __launch_bounds__(256, 2) void hnsw_upper_table64_kernel(const float*
     table64_block<METRIC, N16>(rows, nu, q, qstride, b, table, nu_pad, blockIdx.x, blockIdx.y);
 }
 
-mdb_status hnsw_upper_table(mdb_ctx* ctx, const HnswUpper& up, int metric, const DistPlan& p, const float* d_q, int qstride, size_t b,
-                            uint32_t* d_table, unsigned long long* zero16) {
-    const uint32_t nu_pad = (uint32_t)up.tiles.ntiles * MDB_TILE;
-    const float4* tiles = (const float4*)up.tiles.data.p;
-    if (up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 && (long long)b >= ctx->opt.hnsw_table64_min_b) {
-        const unsigned gx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), gy = (unsigned)((b + 63) / 64);
-        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-            return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
-                return mdb_launch(ctx, hnsw_upper_table64_kernel<M(), N()>, dim3(gx, gy), 256, 0, up.rows_nat.p, up.nu, d_q, qstride, (uint32_t)b, d_table,
-                                  nu_pad, zero16);
-            });
-        }));
-        MDB_HIP(ctx, hipGetLastError());
-        return MDB_OK;
-    }
-    if (p.n16 > 0 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0) {
-        const unsigned gx = (unsigned)((up.tiles.ntiles + 3) / 4);
-        const int qf = ctx->opt.hnsw_table_qt == 8 ? 8 : ctx->opt.hnsw_table_qt == 2 ? 2 : 4;
-        MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-            const uint32_t full = (uint32_t)(b / qf), rest = (uint32_t)(b % qf);
-            if (full)
-                MDB_TRY(mdb_pick<8, 4, 2>(qf, [&](auto QF) {
-                    return mdb_launch(ctx, hnsw_upper_table16_kernel<M(), QF()>, dim3(gx, full), 256, 0, tiles, up.nu, (uint32_t)up.tiles.ntiles, p.n16,
-                                      d_q, qstride, 0u, d_table, nu_pad, zero16);
-                }));
-            if (rest)
-                MDB_TRY(mdb_launch(ctx, hnsw_upper_table16_kernel<M(), 1>, dim3(gx, rest), 256, 0, tiles, up.nu, (uint32_t)up.tiles.ntiles, p.n16, d_q,
-                                   qstride, full * qf, d_table, nu_pad, full * qf == 0u ? zero16 : nullptr));
-            return MDB_OK;
-        }));
-        MDB_HIP(ctx, hipGetLastError());
-        return MDB_OK;
-    }
-    constexpr int QT = 2;   // any dimension: the cascade of exact_sums
-    const uint32_t full = (uint32_t)(b / QT), rest = (uint32_t)(b % QT);
-    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-        if (full)
-            MDB_TRY(mdb_launch(ctx, hnsw_upper_table_kernel<M(), QT>, dim3((unsigned)up.tiles.ntiles, full), 64, 0, tiles, up.nu, p, d_q, qstride, 0u,
-                               d_table, nu_pad, zero16));
-        if (rest)
-            MDB_TRY(mdb_launch(ctx, hnsw_upper_table_kernel<M(), 1>, dim3((unsigned)up.tiles.ntiles, rest), 64, 0, tiles, up.nu, p, d_q, qstride,
-                               full * QT, d_table, nu_pad, full ? nullptr : zero16));
-        return MDB_OK;
-    }));
-    MDB_HIP(ctx, hipGetLastError());
-    return MDB_OK;
-}
-
 // ------------------------------------------------------------------------------------------ traversal
 struct HnswUpArgs {
     const uint32_t* rows;     // [(layer - row_layer0) * nu + c] * su: adjacency rows of layers row_layer0 .. in this launch's compact numbering
@@ -297,14 +249,7 @@ struct HnswUpArgs {
     uint32_t top_n;
     int cl_tlds;              // closure launch behind the table: the query's row is copied into LDS
 };
-// roles of a launch in the fallback protocol (HnswUpArgs::fb_role)
-#define CL_ROLE_NONE 0
-#define CL_ROLE_TOP 1            // closure, the split path's top launch: fb[q] = flagged (the counter words are being cleared by this very launch)
-#define CL_ROLE_BOTTOM 2         // closure behind CL_ROLE_TOP / _TOP_LOCAL: a query left flagged above is skipped; counted when flagged here or above
-#define CL_ROLE_SINGLE 3         // closure over every upper layer: fb[q] = flagged, counted
-#define CL_ROLE_FALLBACK 4       // the sequential kernels: blocks of unflagged queries exit at once
-#define CL_ROLE_TOP_LOCAL 5      // CL_ROLE_TOP whose block re-runs a flagged query itself, on sorted positions: every query is handed over,
-                                 // fb[q] = CL_FB_COUNT marks the flagged ones for the launch below to count
+// (the CL_ROLE_* roles of a launch in the fallback protocol, HnswUpArgs::fb_role: mdb_hnsw_route.h)
 // values of fb[q]; every call writes the word of each of its queries before it reads it (the scratch is reused from call to call)
 #define CL_FB_CLEAN 0u
 #define CL_FB_RERUN 1u           // the follow-up launch re-runs the query: from the top, or layer 1 alone behind CL_ROLE_TOP_LOCAL
@@ -314,7 +259,7 @@ struct HnswUpArgs {
 #define UP_LDS_STAGE 0                 // 512 keys (compaction staging)
 #define UP_LDS_FLAG 4096               // 512 words
 #define UP_LDS_FR 6144                 // two frontier lists of 64 (closure of tiny layers)
-#define UP_LDS_VIS 6656
+// UP_LDS_VIS 6656 (mdb_hnsw_route.h): the visited set, then what the launch's form puts behind it
 
 // One wave per query.  The state is the Beam<NB> of mdb_hnsw_dev.hip.h and the step a sequence of its operations (over-full
 // unsorted register beam B, acceptance and stop test by counting, runner-up + its row fetched ahead) — the step hnsw_beam_kernel's
@@ -323,7 +268,6 @@ struct HnswUpArgs {
 // a lookup is then an LDS read (~100 cycles) instead of a first-touch miss of a line the table kernel wrote from another XCD
 // (the L2s are not coherent: the row comes back from the Infinity Cache / HBM, ~1 k cycles, 40 % of the lookups).  Waves 1-3 only
 // help with that copy.
-#define UP_BLOCK 256
 // wave 0 of the block (64 lanes): layers a.layer_hi .. a.layer_lo on the table row `tq`, visited set `vis` (LDS, initialised by the
 // caller), then the hand-over.  `vis_out`: LDS scratch of a.out_words words when a.vis_map is set.
 template <int NB>
@@ -714,166 +658,106 @@ __global__ __launch_bounds__(256, 2) void hnsw_upper_top_rank_kernel(HnswUpArgs 
     else upper_traverse_rank<NW>(a, qi, lane, lds, R, P, nan_start, vis, vis_out, __builtin_readcyclecounter() - ts0);
 }
 
-// launch of hnsw_upper_kernel over layers layer_hi .. 1 (the last launch before layer 0: out_ep holds point ids, the bitmap as is)
-// fb: this is the fallback launch behind the frontier form — only the queries it flagged run
-static mdb_status upper_launch_bottom(mdb_ctx* ctx, const HnswUpper& up, const uint32_t* d_table, size_t b, uint32_t ef, const HnswUpperOut& out,
-                                      int layer_hi, const uint32_t* in_ep, const uint32_t* in_ovf, const uint32_t* in_vis, const uint32_t* in_cnt,
-                                      uint32_t* fb = nullptr) {
+// ------------------------------------------------------------------------------------------ executor
+// The arguments of a traversal launch of the route, by its role.  HR_TOP: the TOP set (layers >= 2) on a row the block evaluates itself,
+// handing entry point and visited set on in the layer-1 numbering, overflow flag and counters not yet counted (st: the hand-over
+// state, fb behind it).  HR_LAYER1 / HR_FALLBACK: layers l.layer_hi .. 1 on the table rows, the last launch before layer 0 (out_ep
+// holds point ids, the bitmap as is).
+static HnswUpArgs upper_args(mdb_ctx* ctx, const HnswUpper& up, const DistPlan& p, const float* d_q, int qstride, const HnswRoute& r,
+                             const HnswLaunch& l, const uint32_t* d_table, uint32_t* st, const HnswUpperOut& out) {
+    const bool top = l.role == HR_TOP;
+    uint32_t *const st_ep = st, *const st_ovf = st + r.st_ovf, *const st_cnt = st + r.st_cnt, *const st_vis = st + r.st_vis;
     HnswUpArgs a{};
-    a.fb = fb; a.fb_role = fb ? CL_ROLE_FALLBACK : CL_ROLE_NONE;
-    a.rows = up.rows.p; a.table = d_table; a.row_layer0 = 1;
-    a.nu = up.nu; a.nu_pad = (uint32_t)up.tiles.ntiles * MDB_TILE; a.su = up.su; a.small_layer = up.small_layer;
-    a.entry_c = up.entry_c;
-    a.layer_hi = layer_hi; a.layer_lo = 1;
-    a.ef = (int)ef;
-    a.vis_words = out.words;
-    a.in_ep = in_ep; a.in_ovf = in_ovf; a.in_vis = in_vis; a.in_cnt = in_cnt;
-    a.ep_map = up.ids.p; a.vis_map = nullptr; a.out_words = out.words;
-    a.out_ep = out.ep; a.out_ovf = out.ovf; a.out_vis = out.vis; a.out_cnt = out.cnt;
+    a.rows = top ? up.rows2.p : up.rows.p; a.table = top ? nullptr : d_table; a.row_layer0 = top ? 2 : 1;
+    a.nu = top ? up.nu2 : up.nu; a.nu_pad = top ? r.nu2_pad : r.nu_pad; a.su = up.su; a.small_layer = up.small_layer;
+    a.entry_c = top ? up.entry_c2 : up.entry_c;
+    a.layer_hi = l.layer_hi; a.layer_lo = top ? 2 : 1;
+    a.ef = (int)r.ef;
+    a.vis_words = top ? r.up_words2 : r.up_words;
+    if (l.handover) { a.in_ep = st_ep; a.in_ovf = st_ovf; a.in_vis = st_vis; a.in_cnt = st_cnt; }
+    a.ep_map = top ? up.map21.p : up.ids.p; a.vis_map = top ? up.map21.p : nullptr; a.out_words = r.up_words;
+    a.out_ep = top ? st_ep : out.ep; a.out_ovf = top ? st_ovf : out.ovf; a.out_vis = top ? st_vis : out.vis; a.out_cnt = top ? st_cnt : out.cnt;
     a.flags = ctx->d_flags; a.counters = ctx->d_counters;
-    a.dbg_on = (int)(ctx->opt.hnsw_dbg & 1);
-    // sorted positions (mdb_hnsw_rank.hip.h): the block sorts its table row and traverses by ranks — any ef, no beam registers
-    {
-        const size_t rlds = rk_lds_bytes(out.words, a.nu_pad, RK_BLOCK, 0);
-        if ((ctx->opt.hnsw_rank & 1) && a.nu <= RK_MAX_POINTS && a.nu_pad <= RK_MAX_POINTS && rlds <= 160 * 1024 - 512) {
-            MDB_TRY(mdb_pick<1, 4, 16>(a.nu_pad <= 2048 ? 1 : a.nu_pad <= 8192 ? 4 : 16, [&](auto NW) {
-                return mdb_launch(ctx, hnsw_upper_rank_kernel<NW()>, dim3((unsigned)b), RK_BLOCK, rlds, a);
-            }));
-            MDB_HIP(ctx, hipGetLastError());
-            return MDB_OK;
-        }
+    if (top) {
+        a.self_tiles = (const float4*)up.tiles2.data.p; a.self_ntiles = (uint32_t)up.tiles2.ntiles; a.n16 = p.n16; a.q = d_q; a.qstride = qstride;
     }
-    const size_t lds_base = UP_LDS_VIS + (size_t)out.words * 4;
-    const bool tlds = lds_base + (size_t)a.nu_pad * 4 <= 160 * 1024 - 512 && !ctx->opt.hnsw_table_no_lds;
-    const size_t lds = lds_base + (tlds ? (size_t)a.nu_pad * 4 : 0);
-    // registers of 64 beam slots: every count, selection and push of a step loops over them — four when ef leaves them enough slack
-    // (a compaction every ~slack accepted neighbours costs less than a fifth register in every step), five up to 256, eight beyond
-    MDB_TRY(mdb_pick<4, 5, 8>(hnsw_beam_nb4(ctx, ef) ? 4 : ef <= 256 ? 5 : 8, [&](auto NB) {
-        return mdb_pick_bool(tlds, [&](auto TL) { return mdb_launch(ctx, hnsw_upper_kernel<TL(), NB()>, dim3((unsigned)b), UP_BLOCK, lds, a); });
-    }));
-    MDB_HIP(ctx, hipGetLastError());
-    return MDB_OK;
+    // MDB_PIPE_DBG builds (MDB_HNSW_DBG bit 0: the sequential bottom launch, bit 1: the sequential top launch)
+    if (l.fb_role == CL_ROLE_NONE || l.fb_role == CL_ROLE_FALLBACK) a.dbg_on = (int)((ctx->opt.hnsw_dbg >> (top ? 1 : 0)) & 1);
+    if (l.fb_role != CL_ROLE_NONE) { a.fb = st + r.st_fb; a.fb_role = l.fb_role; }
+    if (l.fb_role == CL_ROLE_BOTTOM || l.fb_role == CL_ROLE_SINGLE) {   // the frontier form's own theta over the TOP set
+        if (up.nu2 > 0 && up.map21.p) { a.top_map = up.map21.p; a.top_n = up.nu2; }
+        a.cl_tlds = l.cl_tlds ? 1 : 0;
+    }
+    return a;
 }
 
-mdb_status hnsw_upper_traverse(mdb_ctx* ctx, const HnswUpper& up, const uint32_t* d_table, size_t b, uint32_t ef, const HnswUpperOut& out) {
-    return upper_launch_bottom(ctx, up, d_table, b, ef, out, (int)up.layers, nullptr, nullptr, nullptr, nullptr);
-}
-
-mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, int metric, const DistPlan& p, const float* d_q, int qstride, size_t b,
-                          uint32_t ef, uint32_t* d_table, uint32_t* d_state, const HnswUpperOut& out, unsigned long long* zero16) {
-    const uint32_t nu_pad = (uint32_t)up.tiles.ntiles * MDB_TILE;
-    const uint32_t nu2_pad = (uint32_t)up.tiles2.ntiles * MDB_TILE;
-    const uint32_t words2 = (up.nu2 / 32 + 4) & ~3u;
-    // ---- the frontier form (mdb_hnsw_closure.hip.h): table + top layers, layer 1, then the fallback launch for the flagged queries
-    if (ctx->opt.hnsw_closure && up.su <= 64 && up.layers >= 1) {
-        const size_t lds_lim = 160 * 1024 - 512;
-        const size_t lds_row = cl_lds_words(out.words, 0, nu_pad) * 4, lds_norow = cl_lds_words(out.words, 0, 0) * 4;
-        const bool tlds = lds_row <= lds_lim && !ctx->opt.hnsw_table_no_lds;
-        const size_t lds_ctop = cl_lds_words(words2, out.words, nu2_pad) * 4;
-        const bool csplit = up.nu2 > 0 && up.layers >= 2 && up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 &&
-                            (long long)b >= ctx->opt.hnsw_table64_min_b && !ctx->opt.hnsw_no_split &&
-                            lds_ctop <= 80 * 1024 - 512;   // (two blocks per CU: the table blocks of the same launch share it)
-        if (lds_norow <= lds_lim) {
-            uint32_t* const st_ep = d_state;
-            uint32_t* const st_ovf = st_ep + b;
-            uint32_t* const st_cnt = st_ovf + b;
-            uint32_t* const st_vis = st_cnt + 4 * b;
-            uint32_t* const fb = st_vis + (size_t)b * out.words;   // [b] behind the hand-over state (d_state holds b * (words + 8) + 64 words)
-            HnswUpArgs c{};
-            c.rows = up.rows.p; c.table = d_table; c.row_layer0 = 1;
-            c.nu = up.nu; c.nu_pad = nu_pad; c.su = up.su; c.small_layer = up.small_layer; c.entry_c = up.entry_c;
-            c.layer_hi = (int)up.layers; c.layer_lo = 1;
-            c.ef = (int)ef;
-            c.vis_words = out.words;
-            c.ep_map = up.ids.p; c.vis_map = nullptr; c.out_words = out.words;
-            c.out_ep = out.ep; c.out_ovf = out.ovf; c.out_vis = out.vis; c.out_cnt = out.cnt;
-            c.flags = ctx->d_flags; c.counters = ctx->d_counters;
-            c.fb = fb; c.fb_role = CL_ROLE_SINGLE;
-            if (up.nu2 > 0 && up.map21.p) { c.top_map = up.map21.p; c.top_n = up.nu2; }
-            // a top block re-runs its flagged query itself, on sorted positions (upper_traverse_rank1: <= 2048 ranks), when its LDS
-            // holds that layout as well; the follow-up launch then has layer 1 alone to re-run, from the top launch's hand-over
-            const size_t lds_top_rank = rk_lds_bytes(words2, nu2_pad, 256, nu2_pad + out.words);
-            const bool local = csplit && (ctx->opt.hnsw_rank & 2) && nu2_pad <= 2048 && lds_top_rank <= 80 * 1024 - 512;
-            if (csplit) {
-                HnswUpArgs t{};
-                t.rows = up.rows2.p; t.table = nullptr; t.row_layer0 = 2;
-                t.nu = up.nu2; t.nu_pad = nu2_pad; t.su = up.su; t.small_layer = up.small_layer; t.entry_c = up.entry_c2;
-                t.layer_hi = (int)up.layers; t.layer_lo = 2;
-                t.ef = (int)ef;
-                t.vis_words = words2;
-                t.ep_map = up.map21.p; t.vis_map = up.map21.p; t.out_words = out.words;
-                t.out_ep = st_ep; t.out_ovf = st_ovf; t.out_vis = st_vis; t.out_cnt = st_cnt;
-                t.flags = ctx->d_flags; t.counters = ctx->d_counters;
-                t.self_tiles = (const float4*)up.tiles2.data.p; t.self_ntiles = (uint32_t)up.tiles2.ntiles; t.n16 = p.n16; t.q = d_q; t.qstride = qstride;
-                t.fb = fb; t.fb_role = local ? CL_ROLE_TOP_LOCAL : CL_ROLE_TOP;
-                const unsigned tgx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), tgy = (unsigned)((b + 63) / 64);
-                MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-                    return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
-                        return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), 1>, dim3((unsigned)b + tgx * tgy), 256,
-                                          local && lds_top_rank > lds_ctop ? lds_top_rank : lds_ctop, t, (uint32_t)b,
-                                          up.rows_nat.p, up.nu, d_table, nu_pad, tgx, zero16);
-                    });
-                }));
-                MDB_HIP(ctx, hipGetLastError());
-                c.layer_hi = 1;
-                c.in_ep = st_ep; c.in_ovf = st_ovf; c.in_vis = st_vis; c.in_cnt = st_cnt;
-                c.fb_role = CL_ROLE_BOTTOM;
-            } else {
-                MDB_TRY(hnsw_upper_table(ctx, up, metric, p, d_q, qstride, b, d_table, zero16));
-            }
-            c.cl_tlds = tlds ? 1 : 0;
-            MDB_TRY(mdb_launch(ctx, hnsw_upper_rank_kernel<1>, dim3((unsigned)b), RK_BLOCK, tlds ? lds_row : lds_norow, c));
-            MDB_HIP(ctx, hipGetLastError());
-            // the sequential traversal for the flagged queries (one launch, table rows of the launches above): of layer 1 alone, from the
-            // top launch's hand-over, when the top blocks resolve their own flags — of every upper layer otherwise
-            if (local) return upper_launch_bottom(ctx, up, d_table, b, ef, out, 1, st_ep, st_ovf, st_vis, st_cnt, fb);
-            return upper_launch_bottom(ctx, up, d_table, b, ef, out, (int)up.layers, nullptr, nullptr, nullptr, nullptr, fb);
-        }
-    }
-    const size_t lds_top =UP_LDS_VIS + (size_t)words2 * 4 + (size_t)nu2_pad * 4 + (size_t)out.words * 4;
-    const bool split = up.nu2 > 0 && up.layers >= 2 && up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 &&
-                       (long long)b >= ctx->opt.hnsw_table64_min_b && !ctx->opt.hnsw_no_split && lds_top <= 160 * 1024 - 512 && ef <= 256;
-    // the top blocks on sorted positions: their LDS holds the row, its two rank tables and the sort's histograms
-    const size_t lds_top_rank = rk_lds_bytes(words2, nu2_pad, 256, nu2_pad + out.words);
-    const bool top_rank = (ctx->opt.hnsw_rank & 2) && up.nu2 > 0 && up.layers >= 2 && up.rows_nat.p && p.n16 > 0 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 &&
-                          p.ntail == 0 && (long long)b >= ctx->opt.hnsw_table64_min_b && !ctx->opt.hnsw_no_split && nu2_pad <= 8192 &&
-                          lds_top_rank <= 80 * 1024 - 512;   // (two blocks per CU: the table blocks of the same launch share it)
-    if (!split && !top_rank) {
-        MDB_TRY(hnsw_upper_table(ctx, up, metric, p, d_q, qstride, b, d_table, zero16));
-        return hnsw_upper_traverse(ctx, up, d_table, b, ef, out);
-    }
-    // hand-over between the two launches: entry point and visited set in the layer-1 numbering, overflow flag, counters
-    uint32_t* const st_ep = d_state;
-    uint32_t* const st_ovf = st_ep + b;
-    uint32_t* const st_cnt = st_ovf + b;
-    uint32_t* const st_vis = st_cnt + 4 * b;
-    HnswUpArgs a{};
-    a.rows = up.rows2.p; a.table = nullptr; a.row_layer0 = 2;
-    a.nu = up.nu2; a.nu_pad = nu2_pad; a.su = up.su; a.small_layer = up.small_layer; a.entry_c = up.entry_c2;
-    a.layer_hi = (int)up.layers; a.layer_lo = 2;
-    a.ef = (int)ef;
-    a.vis_words = words2;
-    a.ep_map = up.map21.p; a.vis_map = up.map21.p; a.out_words = out.words;
-    a.out_ep = st_ep; a.out_ovf = st_ovf; a.out_vis = st_vis; a.out_cnt = st_cnt;
-    a.flags = ctx->d_flags; a.counters = ctx->d_counters;
-    a.self_tiles = (const float4*)up.tiles2.data.p; a.self_ntiles = (uint32_t)up.tiles2.ntiles; a.n16 = p.n16; a.q = d_q; a.qstride = qstride;
-    a.dbg_on = (int)((ctx->opt.hnsw_dbg >> 1) & 1);
-    const unsigned tgx = (unsigned)((up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW)), tgy = (unsigned)((b + 63) / 64);
-    const unsigned grid = (unsigned)b + tgx * tgy;
-    const bool nb4 = hnsw_beam_nb4(ctx, ef);
-    MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(metric, [&](auto M) {
-        return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(p.n16, [&](auto N) {
-            if (top_rank)
-                return mdb_pick<1, 4>(nu2_pad <= 2048 ? 1 : 4, [&](auto NW) {
-                    return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), NW()>, dim3(grid), 256, lds_top_rank, a, (uint32_t)b, up.rows_nat.p, up.nu,
-                                      d_table, nu_pad, tgx, zero16);
+mdb_status hnsw_upper_run(mdb_ctx* ctx, const HnswUpper& up, const DistPlan& p, const float* d_q, int qstride, size_t b,
+                          const HnswRoute& r, uint32_t* d_table, uint32_t* d_state, const HnswUpperOut& out, unsigned long long* zero16) {
+    const float4* tiles = (const float4*)up.tiles.data.p;
+    const uint32_t ntiles = (uint32_t)up.tiles.ntiles, tgx = (up.nu + 4 * T64_PPW - 1) / (4 * T64_PPW);
+    for (int i = 0; i < r.n; ++i) {
+        const HnswLaunch& l = r.launch[i];
+        if (l.role != HR_TABLE && l.role != HR_TOP && l.role != HR_LAYER1 && l.role != HR_FALLBACK) continue;
+        const dim3 grid(l.gx, l.gy);
+        unsigned long long* const z16 = l.zero16 ? zero16 : nullptr;
+        const HnswUpArgs a = l.role == HR_TABLE ? HnswUpArgs{} : upper_args(ctx, up, p, d_q, qstride, r, l, d_table, d_state, out);
+        switch (l.kernel) {
+        case HK_TABLE64:
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(l.targ[0], [&](auto M) {
+                return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(l.targ[1], [&](auto N) {
+                    return mdb_launch(ctx, hnsw_upper_table64_kernel<M(), N()>, grid, l.block, l.lds, up.rows_nat.p, up.nu, d_q, qstride, (uint32_t)b,
+                                      d_table, r.nu_pad, z16);
                 });
-            return mdb_pick<4, 5>(nb4 ? 4 : 5, [&](auto NB) {
-                return mdb_launch(ctx, hnsw_upper_top_kernel<M(), N(), NB()>, dim3(grid), 256, lds_top, a, (uint32_t)b, up.rows_nat.p, up.nu, d_table,
-                                  nu_pad, tgx, zero16);
-            });
-        });
-    }));
-    MDB_HIP(ctx, hipGetLastError());
-    return upper_launch_bottom(ctx, up, d_table, b, ef, out, 1, st_ep, st_ovf, st_vis, st_cnt);
+            }));
+            break;
+        case HK_TABLE16:
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(l.targ[0], [&](auto M) {
+                return mdb_pick<8, 4, 2, 1>(l.targ[1], [&](auto QF) {
+                    return mdb_launch(ctx, hnsw_upper_table16_kernel<M(), QF()>, grid, l.block, l.lds, tiles, up.nu, ntiles, p.n16, d_q, qstride,
+                                      l.q_first, d_table, r.nu_pad, z16);
+                });
+            }));
+            break;
+        case HK_TABLE:
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(l.targ[0], [&](auto M) {
+                return mdb_pick<2, 1>(l.targ[1], [&](auto QT) {
+                    return mdb_launch(ctx, hnsw_upper_table_kernel<M(), QT()>, grid, l.block, l.lds, tiles, up.nu, p, d_q, qstride, l.q_first, d_table,
+                                      r.nu_pad, z16);
+                });
+            }));
+            break;
+        case HK_TOP_RANK:
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(l.targ[0], [&](auto M) {
+                return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(l.targ[1], [&](auto N) {
+                    return mdb_pick<1, 4>(l.targ[2], [&](auto NW) {
+                        return mdb_launch(ctx, hnsw_upper_top_rank_kernel<M(), N(), NW()>, grid, l.block, l.lds, a, (uint32_t)b, up.rows_nat.p, up.nu,
+                                          d_table, r.nu_pad, tgx, z16);
+                    });
+                });
+            }));
+            break;
+        case HK_TOP:
+            MDB_TRY(mdb_pick<MDB_METRIC_L2, MDB_METRIC_DOT>(l.targ[0], [&](auto M) {
+                return mdb_pick<1, 2, 3, 4, 5, 6, 7, 8>(l.targ[1], [&](auto N) {
+                    return mdb_pick<4, 5>(l.targ[2], [&](auto NB) {
+                        return mdb_launch(ctx, hnsw_upper_top_kernel<M(), N(), NB()>, grid, l.block, l.lds, a, (uint32_t)b, up.rows_nat.p, up.nu, d_table,
+                                          r.nu_pad, tgx, z16);
+                    });
+                });
+            }));
+            break;
+        case HK_UPPER_RANK:
+            MDB_TRY(mdb_pick<1, 4, 16>(l.targ[0], [&](auto NW) { return mdb_launch(ctx, hnsw_upper_rank_kernel<NW()>, grid, l.block, l.lds, a); }));
+            break;
+        case HK_UPPER:
+            MDB_TRY(mdb_pick<4, 5, 8>(l.targ[1], [&](auto NB) {
+                return mdb_pick_bool(l.targ[0] != 0, [&](auto TL) { return mdb_launch(ctx, hnsw_upper_kernel<TL(), NB()>, grid, l.block, l.lds, a); });
+            }));
+            break;
+        default:
+            return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "hnsw_upper_run: a route with kernel %d among its upper launches", (int)l.kernel);
+        }
+        MDB_HIP(ctx, hipGetLastError());
+    }
+    return MDB_OK;
 }

@@ -443,6 +443,13 @@ class BlockBasedIvf:
 
 
 # ------------------------------------------------------------------------------------------ HNSW
+def parse_route_line(line):
+    """`role kernel_key gx,gy block lds` (a kernel key has blanks of its own) -> (role, key, (gx, gy), block, lds)"""
+    role, rest = line.split(" ", 1)
+    key, grid, block, lds = rest.rsplit(" ", 3)
+    return role, key, tuple(int(g) for g in grid.split(",")), int(block), int(lds)
+
+
 class BlockBasedHnsw:
     """rs/index/src/hnsw/block_based/index.rs"""
 
@@ -484,6 +491,16 @@ class BlockBasedHnsw:
         self.ctx.check(self.ctx.lib.mdb_hnsw_ann_search(self.h, L.ptr(q, C.c_float), C.c_size_t(b), C.c_size_t(k),
                                                         C.c_uint32(ef), C.c_int(L.MEM_HOST), *out.args()))
         return out.result()
+
+    def describe_search(self, b, k, ef, per_query_users=False):
+        """mdb_hnsw_describe_search: (shape words, [(role, kernel key, grid, block, lds)]) of a search of b queries under the context's
+        current options; launches nothing.  grid is (gx, gy) in blocks."""
+        buf = C.create_string_buffer(4096)
+        self.ctx.check(self.ctx.lib.mdb_hnsw_describe_search(self.h, C.c_size_t(b), C.c_size_t(k), C.c_uint32(ef),
+                                                             C.c_int(int(per_query_users)), buf, C.c_size_t(len(buf))))
+        lines = buf.value.decode().splitlines()
+        assert lines and lines[0].startswith("shape "), lines
+        return lines[0][len("shape "):], [parse_route_line(ln) for ln in lines[1:]]
 
     def ann_search_submit(self, queries, k, ef):
         """mdb_hnsw_ann_search_submit: enqueue and return; Pending.wait() gives the SearchResult."""

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "mdb_multi_spann_search_filtered", "mdb_multi_spann_attach", "mdb_multi_spann_search_submit",
     "mdb_set_option", "mdb_get_option", "mdb_points_block_bytes", "mdb_points_block_views", "mdb_ivf_search_shard", "mdb_ivf_merge_shards",
     "mdb_spann_search_shard", "mdb_spann_merge_shards", "mdb_multi_spann_search_shard", "mdb_multi_spann_merge_shards", "mdb_spann_probe_row_words", "mdb_multi_spann_probes", "mdb_multi_spann_search_shard_probes",
-    "mdb_allgather_blocks", "mdb_device_mem_info", "mdb_hnsw_closure_fallbacks",
+    "mdb_allgather_blocks", "mdb_device_mem_info", "mdb_hnsw_closure_fallbacks", "mdb_hnsw_describe_search",
     "mdb_hnsw_check_files", "mdb_ivf_check_files", "mdb_spann_check_files", "mdb_multi_spann_check_files",
 ]
 

@@ -30,6 +30,48 @@ def disassemble(workdir, obj):
     return subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", obj], cwd=str(workdir), check=True, capture_output=True, text=True).stdout
 
 
+def host_cxx():
+    """(compiler, extra flags) for a host program whose sanitizer runtimes are linked STATICALLY (it then runs in whatever environment
+    the suite runs in); clang++ links them statically by default."""
+    for cxx, flags in (("/opt/rocm/llvm/bin/clang++", []), ("clang++", []), ("g++", ["-static-libasan", "-static-libubsan"])):
+        path = shutil.which(cxx)
+        if path:
+            return path, flags
+    return None, []
+
+
+def build_route_program(exe, sanitize=False):
+    """tests/host/hnsw_route_main.cpp (the HNSW route header alone, muopdb_amd/csrc/mdb_hnsw_route.h) -> `exe`"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx, static_runtime = host_cxx()
+    assert cxx, "no host C++ compiler"
+    san = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *static_runtime] if sanitize else []
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", *san, os.path.join(root, "tests", "host", "hnsw_route_main.cpp"), "-o", str(exe)],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-4000:]
+    return str(exe)
+
+
+def run_route_program(exe, case_lines):
+    """one route per case line: [(launch lines, {"launches" | "scratch" | "facts": text})]; `unsupported` -> (None, {})"""
+    run = subprocess.run([exe], input="\n".join(case_lines) + "\n", capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and not run.stderr, "exit %d\n%s" % (run.returncode, run.stderr[-4000:])
+    routes, launches, notes = [], [], {}
+    for line in run.stdout.splitlines():
+        if line == "end":
+            routes.append((launches, notes))
+            launches, notes = [], {}
+        elif line == "unsupported":
+            launches = None
+        elif line.startswith("# "):
+            name, text = line[2:].split(" ", 1) if " " in line[2:] else (line[2:], "")
+            notes[name] = text
+        else:
+            launches.append(line)
+    assert len(routes) == len(case_lines), (len(routes), len(case_lines))
+    return routes, run.stdout
+
+
 def kernel_key(name):
     """A kernel's demangled name without return type, parameter list and descriptor suffix: `ivf_scan_pq3_kernel<4, 512, true>`.
     The same key comes out of a `.kd` symbol of a code object and of a profiler's kernel name."""

@@ -328,13 +328,37 @@ def _hnsw_pair(oracle, ctx, index, vf, d, metric):
             oracle.BlockBasedHnsw(index, vf, d, oracle.Quant(oracle.QUANT_NONE, metric)))
 
 
-def _hnsw_check(ctx, g, o, q, k, ef, opts):
+def _nf(d):
+    """N16T of the layer-0 kernels"""
+    return {768: 48, 128: 8}.get(d, 0)
+
+
+def _tf(v):
+    return "true" if v else "false"
+
+
+def _l0_key(form, d, metric, vis_lds):
+    """the layer-0 kernel key of a form of HNSW_FORMS, written out from the comment above them"""
+    head = "%d, %s, %d" % (metric, _tf(vis_lds), _nf(d))
+    nb = {"nb4-ef64": 4, "nb4-ef200": 4, "nb5-ef230": 5, "nb5-slack0-ef64": 5, "nb8-ef300": 8}.get(form)
+    if nb:
+        return "hnsw_beam_kernel<%s, true, true, %d>" % (head, nb)
+    if form.startswith("general"):
+        return "hnsw_search_kernel<%s>" % head
+    return "hnsw_beam_kernel<%s, %s, false, 5>" % (head, _tf(form.startswith("no_table")))
+
+
+def _hnsw_check(ctx, g, o, q, k, ef, opts, keys=None):
+    """keys: the kernel keys mdb_hnsw_describe_search names for this call under `opts`, in launch order (a str: the last one's)"""
     o.stats()
     want = o.ann_search(q, k, ef)
     evals, expanded = o.stats()
     ctx.stats()
     with options(ctx, **opts):
         got = g.ann_search(q, k, ef)
+        described = [key for _, key, _, _, _ in g.describe_search(len(q), k, ef)[1]]
+    if keys is not None:
+        assert (described[-1] if isinstance(keys, str) else described) == keys, (ef, opts, described)
     st = ctx.stats()
     assert_result_rows(got, want, len(q))
     assert (st["distance_evals"], st["expanded_nodes"]) == (evals, expanded), (ef, opts)
@@ -363,7 +387,7 @@ def test_hnsw_layer0_forms_lds_visited(ctx, oracle, hnsw_graph, form, ef, opts, 
     d, hidx, hvec, q = hnsw_graph
     g, o = _hnsw_pair(oracle, ctx, hidx, hvec, d, metric)
     for b in (20, 3):
-        _hnsw_check(ctx, g, o, q[:b], 10, ef, opts)
+        _hnsw_check(ctx, g, o, q[:b], 10, ef, opts, _l0_key(form, d, metric, True))
     g.close()
 
 
@@ -403,7 +427,7 @@ def test_hnsw_layer0_forms_hbm_visited(ctx, oracle, hnsw_big_graph, metric):
     d, index, vf, q = hnsw_big_graph
     g, o = _hnsw_pair(oracle, ctx, index, vf, d, metric)
     for form, ef, opts in HNSW_FORMS:
-        _hnsw_check(ctx, g, o, q, 10, ef, opts)
+        _hnsw_check(ctx, g, o, q, 10, ef, opts, _l0_key(form, d, metric, False))
     g.close()
 
 
@@ -419,9 +443,9 @@ def test_hnsw_closure_forms_dot(ctx, oracle, d):
     q = (v[rng.integers(0, n, 300)] + rng.normal(0, 0.02, (300, d))).astype(np.float32)
     for metric in (L2, DOT):
         g, o = _hnsw_pair(oracle, ctx, hidx, hvec, d, metric)
-        _hnsw_check(ctx, g, o, q[:40], 10, 200, dict())
-        _hnsw_check(ctx, g, o, q[:40], 10, 200, dict(MDB_CLOSURE_BLOCK=256))
-        _hnsw_check(ctx, g, o, q, 10, 200, dict())
+        _hnsw_check(ctx, g, o, q[:40], 10, 200, dict(), ["hnsw_closure_kernel<%d, %d, 1024>" % (metric, _nf(d))])
+        _hnsw_check(ctx, g, o, q[:40], 10, 200, dict(MDB_CLOSURE_BLOCK=256), ["hnsw_closure_kernel<%d, %d, 256>" % (metric, _nf(d))])
+        _hnsw_check(ctx, g, o, q, 10, 200, dict(), ["hnsw_closure_kernel<%d, %d, 256>" % (metric, _nf(d))])
         g.close()
 
 
@@ -430,9 +454,10 @@ def test_hnsw_closure_forms_dot(ctx, oracle, d):
 @pytest.mark.parametrize("n16", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_hnsw_upper_layer_kernels_by_dimension(ctx, oracle, n16, metric):
     """the lane = query kernels are compiled per 16-chunk count (d = 16 .. 128), at batch >= MDB_HNSW_TABLE64_MIN_B (32) on a graph
-    with two upper layers: hnsw_upper_top_rank_kernel<METRIC, N16, 1> by default (at most 2 048 points above layer 1),
-    hnsw_upper_top_kernel<METRIC, N16, 4 | 5> with MDB_HNSW_RANK=0 (ef + 48 <= 256 | beyond), hnsw_upper_table64_kernel<METRIC, N16>
-    with MDB_HNSW_NO_SPLIT"""
+    with two upper layers: hnsw_upper_top_rank_kernel<METRIC, N16, 1> by default (at most 2 048 points above layer 1) — in the frontier
+    form whatever MDB_HNSW_RANK says —, hnsw_upper_top_kernel<METRIC, N16, 4 | 5> with MDB_HNSW_RANK=0 and MDB_HNSW_CLOSURE=0
+    (ef + 48 <= 256 | beyond), hnsw_upper_table64_kernel<METRIC, N16> with MDB_HNSW_NO_SPLIT.  The route (mdb_hnsw_describe_search)
+    names exactly these; under the dot metric d = 16 is a remainder chunk (n16 = 0): the generic table kernel, no top launch."""
     d, n = 16 * n16, 2500
     v = H.sift_like(n, d, n_clusters=16, seed=n16)
     v = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
@@ -440,16 +465,29 @@ def test_hnsw_upper_layer_kernels_by_dimension(ctx, oracle, n16, metric):
     g, o = _hnsw_pair(oracle, ctx, hidx, hvec, d, metric)
     rng = np.random.default_rng(n16)
     q = (v[rng.integers(0, n, 40)] + rng.normal(0, 0.03, (40, d))).astype(np.float32)
+    whole16 = not (metric == DOT and n16 == 1)
+    m_n = "%d, %d" % (metric, n16)
     for ef in (100, 230):
-        for opts in (dict(), dict(MDB_HNSW_RANK=0), dict(MDB_HNSW_NO_SPLIT=1), dict(MDB_HNSW_RANK=0, MDB_HNSW_NO_SPLIT=1)):
-            _hnsw_check(ctx, g, o, q, 10, ef, opts)
+        nb = 4 if ef + 48 <= 256 else 5
+        rank1, upper = "hnsw_upper_rank_kernel<1>", "hnsw_upper_kernel<true, %d>" % nb
+        l0 = "hnsw_beam_kernel<%d, true, %d, true, true, %d>" % (metric, _nf(d), nb)
+        table = "hnsw_upper_table64_kernel<%s>" % m_n if whole16 else "hnsw_upper_table_kernel<1, 2>"
+        top = "hnsw_upper_top_rank_kernel<%s, 1>" % m_n if whole16 else table
+        top_beam = "hnsw_upper_top_kernel<%s, %d>" % (m_n, nb) if whole16 else table
+        for opts, keys in ((dict(), [top, rank1, upper, l0]), (dict(MDB_HNSW_RANK=0), [top, rank1, upper, l0]),
+                           (dict(MDB_HNSW_NO_SPLIT=1), [table, rank1, upper, l0]),
+                           (dict(MDB_HNSW_RANK=0, MDB_HNSW_NO_SPLIT=1), [table, rank1, upper, l0]),
+                           (dict(MDB_HNSW_CLOSURE=0), [top, upper, l0]), (dict(MDB_HNSW_RANK=0, MDB_HNSW_CLOSURE=0), [top_beam, upper, l0])):
+            _hnsw_check(ctx, g, o, q, 10, ef, opts, keys)
     g.close()
 
 
 @pytest.mark.parametrize("n16", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_hnsw_upper_rank_kernels_wide_top(ctx, oracle, n16):
     """more than 2 048 points above layer 1 (2 500 of 6 000 upper-layer points, 40 000 in all): hnsw_upper_top_rank_kernel<METRIC,
-    N16, 4> under both metrics, and hnsw_upper_rank_kernel<4> (MDB_HNSW_RANK=3: 2 049 .. 8 192 upper-layer points) behind it"""
+    N16, 4> under both metrics (the sequential form, MDB_HNSW_CLOSURE=0: the frontier form's top launch is the <.., 1> instance, its
+    blocks then leave the flagged queries to the fallback launch), and hnsw_upper_rank_kernel<4> (MDB_HNSW_RANK=3: 2 049 .. 8 192
+    upper-layer points) behind it.  The route (mdb_hnsw_describe_search) names exactly these."""
     from muopdb_amd import formats as F
     d, n = 16 * n16, 40_000
     rng = np.random.default_rng(100 + n16)
@@ -462,8 +500,14 @@ def test_hnsw_upper_rank_kernels_wide_top(ctx, oracle, n16):
     q = (v[rng.integers(0, n, 40)] + rng.normal(0, 0.02, (40, d))).astype(np.float32)
     for metric in (L2, DOT):
         g, o = _hnsw_pair(oracle, ctx, index, vf, d, metric)
-        for opts in (dict(), dict(MDB_HNSW_RANK=3)):
-            _hnsw_check(ctx, g, o, q, 10, 100, opts)
+        whole16 = not (metric == DOT and n16 == 1)
+        table = "hnsw_upper_table_kernel<1, 2>"
+        top1, top4 = [("hnsw_upper_top_rank_kernel<%d, %d, %d>" % (metric, n16, nw)) if whole16 else table for nw in (1, 4)]
+        rank1, rank4, upper = "hnsw_upper_rank_kernel<1>", "hnsw_upper_rank_kernel<4>", "hnsw_upper_kernel<true, 4>"
+        l0 = "hnsw_beam_kernel<%d, true, %d, true, true, 4>" % (metric, _nf(d))
+        for opts, keys in ((dict(), [top1, rank1, upper, l0]), (dict(MDB_HNSW_RANK=3), [top1, rank1, rank4, l0]),
+                           (dict(MDB_HNSW_CLOSURE=0), [top4, upper, l0]), (dict(MDB_HNSW_CLOSURE=0, MDB_HNSW_RANK=3), [top4, rank4, l0])):
+            _hnsw_check(ctx, g, o, q, 10, 100, opts, keys)
         g.close()
 
 

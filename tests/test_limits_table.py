@@ -44,10 +44,11 @@ def test_the_two_tables_are_the_same():
 
 
 def test_documented_numbers_follow_the_sources():
-    max_k = define(read(CSRC, "mdb_common.h"), "MDB_MAX_K")
+    max_k = define(read(CSRC, "mdb_files.h"), "MDB_MAX_K")
     hnsw = read(CSRC, "mdb_hnsw.hip")
     stride = define(hnsw, "HNSW_MAX_STRIDE")
-    assert "ef > MDB_MAX_K * 2" in hnsw and "o.num_layers > 255" in hnsw            # the checks the table's ef and layer limits restate
+    # the checks the table's ef and layer limits restate (the ef limit is the route's: mdb_hnsw_route.h)
+    assert "ef > MDB_MAX_K * 2" in read(CSRC, "mdb_hnsw_route.h") and "o.num_layers > 255" in hnsw
     assert "max_neighbors > 64" in read(CSRC, "mdb_hnsw_build.hip")
     assert "num_bits must be 1..8" in read(CSRC, "mdb_core.hip")
     # the loaders' own limits are checked by their host half (mdb_files.cpp), with numbers the kernels' file holds equal to its own
@@ -71,7 +72,7 @@ def test_documented_numbers_follow_the_sources():
 
 
 def test_documented_merge_capacities_follow_the_formulas_in_the_sources():
-    max_k = define(read(CSRC, "mdb_common.h"), "MDB_MAX_K")
+    max_k = define(read(CSRC, "mdb_files.h"), "MDB_MAX_K")
     ivf, spann = read(CSRC, "mdb_ivf.hip"), read(CSRC, "mdb_spann.hip")
     # IvfSet::merge_points and merge_shards_launch: the formulas and the budget as the table states them
     assert "lds = world * k * 8 + k * 20 + (world + 1) * 4 + 16;\n    if (lds > 150 * 1024)" in ivf
