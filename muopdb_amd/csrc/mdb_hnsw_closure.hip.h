@@ -3,9 +3,9 @@
 //
 // Every distance a layer >= 1 can ask for is in the table row T[q][.] before its traversal starts, and everything the layer hands on
 // is a union, a count or a minimum: the visited set, the evaluations (points newly visited), the expansions (expanded points with a
-// non-empty row) and the nearest evaluated point.  Let theta be the ef-th smallest canonical image of the row (index ef - 1 of the
-// sorted row; +inf for a set of <= ef points) and call a point CERTAIN when d < theta.  At most ef - 2 other points are as near as a
-// certain point c, so
+// non-empty row) and the nearest evaluated point.  Let theta be NO LARGER than the ef-th smallest canonical image of the row (index
+// ef - 1 of the sorted row; +inf for a set of <= ef points; cl_theta takes a histogram bin's lower edge) and call a point CERTAIN when
+// d < theta.  At most ef - 2 other points are as near as a certain point c, so
 //   * c is accepted whenever it is discovered (`|W| < ef or d < furthest` cannot fail), and is never evicted;
 //   * the `distance > furthest` break cannot fire when c is popped, nor on anything popped while c is pending (the minimum
 //     candidate is no farther than c).
@@ -18,6 +18,17 @@
 // valid too, only less useful: one select over the launch's row serves its lowest layer, one over the TOP set the layers >= 2 (the
 // split path's top launch numbers exactly that set; a launch over every upper layer reaches it through map21).
 // hnsw_upper_kernel's closure of a layer of <= 64 points is the special case theta = +inf.
+// THE COUNTED STOP TEST.  A single pop happens when the frontiers have run dry: every certain point discovered so far is expanded, so
+// every pending (evaluated, unexpanded) point is uncertain and u is the nearest of them.  An evaluated point closer than u is not
+// pending, hence expanded: a certain point (d < theta <= d_u) or an earlier single pop of this layer.  So
+//     lt = #{evaluated, d <  d_u} = ncert + #{earlier pops p : d_p < d_u}
+//     le = #{evaluated, d <= d_u} = lt + #{pending, d = d_u} + #{earlier pops p : d_p = d_u}
+// with ncert = the certain points evaluated so far (the frontier lengths summed as the rounds read them, the entry point when it is
+// certain), the pending ties counted by the one pass over the bitmap that finds u — each thread keeps how many of its points sit at
+// its own minimum and adds them when that minimum turns out to be d_u — and the earlier pops' images kept in a list of CL_POP_CAP
+// words (in `hist`, idle during the layers; wave 0 counts it).  `lt >= ef` and `le - 1 >= ef` mean what they meant.  A pop that finds
+// the list full flags the query: the sequential form is exact (tests/closure_bound_model.py restates this form and holds it against
+// closure_model.py's scan for every theta up to the exact one).
 // What the counts cannot decide is an uncertain u that passes the strict test while ef OTHER evaluated points are no farther: whether
 // the reference ever accepted u depends on the discovery order.  That, and any evaluated NaN (whose flag the sequential kernels raise
 // where the reference panics), makes the query a FALLBACK: the block publishes nothing (its visited set is a copy in LDS) and the
@@ -55,6 +66,34 @@
 #define CL_SH_MINU 12            // u64: min (image, ~id) over evaluated and unexpanded
 #define CL_SH_MINE 14            // u64: min (image, id) over evaluated
 #define CL_SH_FLAGGED 16         // how closure_traverse ended, for its caller
+#define CL_POP_CAP 256u          // single pops of one layer whose images the block keeps (bench: 8 per block on layer 1, 5 in the top block)
+// MDB_PIPE_DBG builds (mdb_hnsw_dev.hip.h), MDB_HNSW_DBG bit 2: the layer-1 launch, bit 3: the top launch — thread 0's cycle / event sums of the
+// frontier form per call (a batch), in counters[5..15] (word 4 is the fallback counter):
+//   row copy or evaluation | theta (both selects) | per layer: clear + entry point | rounds | trips inside them (count) | rounds (count) |
+//   single pops: both passes | single pops that expanded (count) | hand-over | closure_traverse as a whole | blocks (count)
+#define CL_DBG_ROW 1
+#define CL_DBG_THETA 2
+#define CL_DBG_CLEAR 3
+#define CL_DBG_ROUNDS 4
+#define CL_DBG_NTRIPS 5
+#define CL_DBG_NROUNDS 6
+#define CL_DBG_POPS 7
+#define CL_DBG_NPOPS 8
+#define CL_DBG_HAND 9
+#define CL_DBG_TOTAL 10
+#define CL_DBG_BLOCKS 11
+#ifdef MDB_PIPE_DBG
+#define CL_DBG_NOW() __builtin_readcyclecounter()
+#define CL_DBG_FLUSH()                                                                                  \
+    do {                                                                                                \
+        PIPE_TE(CL_DBG_TOTAL, t_all);                                                                   \
+        if (tid == 0 && a.dbg_on)                                                                       \
+            for (int i = 1; i < 12; ++i) atomicAdd(&a.counters[4 + i], dbg_acc[i]);                     \
+    } while (0)
+#else
+#define CL_DBG_NOW() 0ull
+#define CL_DBG_FLUSH() do {} while (0)
+#endif
 struct ClLds {
     uint32_t *sh, *hist, *fr, *vis, *ev, *ex, *vis_out, *row;
 };
@@ -77,56 +116,66 @@ __device__ __forceinline__ uint64_t cl_wave_min_u64(uint64_t v) {
     const uint32_t lo = wave_min_u32((uint32_t)(v >> 32) == hi ? (uint32_t)v : 0xFFFFFFFFu);
     return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ uint32_t cl_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
 
-// theta: the canonical image at index ef - 1 of the sorted keys[0 .. n) (0xFFFFFFFF = +inf when n <= ef).  Exact block-wide radix
-// select, most significant digit first, over the bits the row's key range has; a NaN sorts last (rk_canon).  idx != nullptr: over
-// keys[idx[0 .. n)] (the TOP set inside the row of all upper points).  Called by every thread.
+// theta: a LOWER BOUND of the canonical image at index ef - 1 of the sorted keys[0 .. n) (0xFFFFFFFF = +inf when n <= ef) — the lower edge
+// of the histogram bin that holds that index after at most two block-wide passes of up to 11 bits each, most significant bits first,
+// over the bits the row's key range has.  Exact for a range below 2^22 images, else the bin is 2^(range bits - 22) images wide.
+// What the header derives from theta is all derived from "at most ef - 2 other points are as near as a point with d < theta", which
+// holds for every value up to the exact one.  A point between the bound and the exact value is uncertain instead of certain: it is
+// popped alone, where the counts let it through (lt <= ef - 2) and cannot flag it (le - 1 <= ef - 2), and expanded as it would have
+// been in a frontier — rows, counters and flags do not depend on the bound (tests/closure_bound_model.py), only the number of single
+// pops does.  A NaN sorts last (rk_canon).  idx != nullptr: over keys[idx[0 .. n)] (the TOP set inside the row of all upper points).
+// The histogram is `hist` and the two frontier lists behind it (idle outside the layers): CL_TH_WORDS = 2048 counters, one per digit;
+// wave 0 scans the sums of 256 groups of 8, then the 8 words of the group that holds the index.  A pass is a block-wide scan of the
+// keys with one LDS add per key: its cost is the passes times the keys per thread, which is why there are two and not five.
+// have_mm: the caller folded the keys' minimum and maximum into the pass that produced the row (mn, mx: this thread's share).
+// Called by every thread.
+#define CL_TH_WORDS (CL_SUBHIST * 256 + 2 * CL_FR_CAP)
+static_assert(CL_TH_WORDS == 2048 && CL_TH_WORDS % 4 == 0, "cl_theta: 256 groups of 8 words, cleared with 16-byte stores");
+static_assert(CL_POP_CAP <= CL_SUBHIST * 256, "the single pops' images live in hist");
 template <int NT>
 __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ idx, const uint32_t n, const uint32_t ef,
-                                             uint32_t* hist, uint32_t* sh) {
+                                             uint32_t* hist, uint32_t* sh, const bool have_mm, uint32_t mn, uint32_t mx) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (n <= ef) return 0xFFFFFFFFu;
     if (tid == 0) { sh[CL_SH_KMIN] = 0xFFFFFFFFu; sh[CL_SH_KMAX] = 0u; }
+    for (int i = tid; i < CL_TH_WORDS / 4; i += NT) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
-    {
-        uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+    if (!have_mm) {
+        mn = 0xFFFFFFFFu; mx = 0u;
         for (uint32_t i = tid; i < n; i += NT) {
             const uint32_t k = rk_canon(keys[idx ? idx[i] : i]);
             mn = min(mn, k);
             mx = max(mx, k);
         }
-        mn = wave_min_u32(mn);
-        mx = wave_max_u32(mx);
-        if (lane == 0) { atomicMin(&sh[CL_SH_KMIN], mn); atomicMax(&sh[CL_SH_KMAX], mx); }
     }
+    mn = wave_min_u32(mn);
+    mx = wave_max_u32(mx);
+    if (lane == 0) { atomicMin(&sh[CL_SH_KMIN], mn); atomicMax(&sh[CL_SH_KMAX], mx); }
     __syncthreads();
     const uint32_t kmin = sh[CL_SH_KMIN], range = sh[CL_SH_KMAX] - kmin;
     int hi = range ? 32 - __builtin_clz(range) : 0;   // bits [lo, hi) are decided by the next pass; the bits above them equal `prefix`
+    if (hi == 0) __syncthreads();                      // (no pass: the words just read are written again by the next select)
     uint32_t prefix = 0u, k = ef - 1u;
-    uint32_t* const hw = hist + (wave & (CL_SUBHIST - 1)) * 256;
-    while (hi > 0) {                                   // (uniform: at most four passes)
-        const int lo = hi > 8 ? hi - 8 : 0;
-        const uint32_t dmask = (1u << (hi - lo)) - 1u;
-        for (int i = tid; i < CL_SUBHIST * 256; i += NT) hist[i] = 0u;
-        __syncthreads();
+    for (int pass = 0; pass < 2 && hi > 0; ++pass) {   // (uniform)
+        const int bits = min(hi, 11), lo = hi - bits;
+        const uint32_t dmask = (1u << bits) - 1u;
+        if (pass) {
+            for (int i = tid; i < CL_TH_WORDS / 4; i += NT) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+            __syncthreads();
+        }
         for (uint32_t i = tid; i < n; i += NT) {
             const uint32_t kp = rk_canon(keys[idx ? idx[i] : i]) - kmin;
             const uint32_t above = hi >= 32 ? 0u : kp >> hi;
-            if (above == prefix) atomicAdd(&hw[(kp >> lo) & dmask], 1u);
+            if (above == prefix) atomicAdd(&hist[(kp >> lo) & dmask], 1u);
         }
         __syncthreads();
-        if (wave == 0) {                               // lane l owns digits 4 l .. 4 l + 3
+        if (wave == 0) {                               // lane l owns the groups 4 l .. 4 l + 3
             uint32_t c[4], tot = 0u;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                c[j] = 0u;
-#pragma unroll
-                for (int s = 0; s < CL_SUBHIST; ++s) c[j] += hist[s * 256 + 4 * lane + j];
+                const uint4 x = ((const uint4*)hist)[2 * (4 * lane + j)], y = ((const uint4*)hist)[2 * (4 * lane + j) + 1];
+                c[j] = x.x + x.y + x.z + x.w + y.x + y.y + y.z + y.w;
                 tot += c[j];
             }
             uint32_t inc = tot;
@@ -139,35 +188,51 @@ __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, 
             if (before <= k && k < inc) {              // exactly one lane
                 int j = 0;
                 while (j < 3 && before + c[j] <= k) { before += c[j]; ++j; }
-                sh[CL_SH_DIGIT] = 4u * lane + j;
+                const uint32_t* const g = hist + 8u * (4u * lane + j);   // the word inside the group
+                uint32_t w = 0u;
+                while (w < 7u && before + g[w] <= k) { before += g[w]; ++w; }
+                sh[CL_SH_DIGIT] = 8u * (4u * lane + j) + w;
                 sh[CL_SH_K] = k - before;
             }
         }
         __syncthreads();
-        prefix = (prefix << (hi - lo)) | sh[CL_SH_DIGIT];
+        prefix = (prefix << bits) | sh[CL_SH_DIGIT];
         k = sh[CL_SH_K];
         hi = lo;
     }
-    return kmin + prefix;
+    return kmin + (prefix << hi);                      // the bin's lower edge: the bits below `hi` stay open
 }
 
 // Layers a.layer_hi .. a.layer_lo of query qi on the table row `tq` (LDS or global memory), by every thread of the block.  L.vis holds
 // the visited set handed in, and the caller's barrier stands behind it and the row.  Publishes the hand-over exactly as
 // upper_traverse_wave0 leaves it, or — flagged — only fb[q] (CL_ROLE_TOP_LOCAL: nothing at all; the caller resolves the flag).
 // Returns the flag, the same for every thread: read back from an LDS word, so that the compiler knows it.
+// have_mm: the caller took the minimum and maximum of the row's canonical images while it produced the row (mn, mx: this thread's share).
 template <int NT>
-__device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int qi, const ClLds& L, const uint32_t* __restrict__ tq) {
+__device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int qi, const ClLds& L, const uint32_t* __restrict__ tq,
+                                                 const bool have_mm, const uint32_t mn, const uint32_t mx, const unsigned long long row_cycles) {
     const int tid = threadIdx.x, lane = tid & 63;
+#ifdef MDB_PIPE_DBG
+    unsigned long long dbg_acc[12] = {0, row_cycles, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+#endif
+    PIPE_T(t_all);
     const uint32_t ef = (uint32_t)a.ef, su = a.su;
     uint32_t gs = 1;                                   // lanes per frontier point: the row stride rounded up to a power of two (<= 64)
     while (gs < su) gs <<= 1;
     const uint32_t per = NT / gs, slot = (uint32_t)tid % gs, sub = (uint32_t)tid / gs;
+    // threads per word of the evaluated bitmap in the single pop's pass (a power of two <= 32): a thread walks its bits one dependent
+    // row lookup after the other, and the TOP set's bitmap is ~32 dense words for 256 threads
+    uint32_t ltpw = 0u;
+    while (ltpw < 5u && (a.vis_words << (ltpw + 1u)) <= (uint32_t)NT) ++ltpw;
+    const uint32_t wbits = 32u >> ltpw, wmask = ltpw ? (1u << wbits) - 1u : 0xFFFFFFFFu;
     uint64_t* const sh_minu = (uint64_t*)(L.sh + CL_SH_MINU);
     uint64_t* const sh_mine = (uint64_t*)(L.sh + CL_SH_MINE);
-    const uint32_t theta = cl_theta<NT>(tq, nullptr, a.nu, ef, L.hist, L.sh);
+    PIPE_T(t_theta);
+    const uint32_t theta = cl_theta<NT>(tq, nullptr, a.nu, ef, L.hist, L.sh, have_mm, mn, mx);
     // one launch over every upper layer: the layers >= 2 hold the TOP set only, and theta of the whole row would leave next to none of
     // its points certain (the layer would be popped one point at a time)
-    const uint32_t theta_top = (a.top_map && a.layer_hi >= 2) ? cl_theta<NT>(tq, a.top_map, a.top_n, ef, L.hist, L.sh) : theta;
+    const uint32_t theta_top = (a.top_map && a.layer_hi >= 2) ? cl_theta<NT>(tq, a.top_map, a.top_n, ef, L.hist, L.sh, false, 0u, 0u) : theta;
+    PIPE_TE(CL_DBG_THETA, t_theta);
     uint32_t ep = a.in_ep ? a.in_ep[qi] : a.entry_c;
     uint32_t evals = a.in_cnt ? a.in_cnt[4 * qi + 0] : 0u, expanded = a.in_cnt ? a.in_cnt[4 * qi + 1] : 0u;
     bool flagged = (a.in_cnt && a.in_cnt[4 * qi + 2]) || (a.in_ovf && a.in_ovf[qi] != 0u) || ep >= a.nu;
@@ -178,9 +243,13 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
         const uint32_t* const lrows = a.rows + (size_t)(layer - a.row_layer0) * a.nu * su;
         // a layer of <= 64 points with edges only among them (ef >= 64): all of it is certain, whatever the row's other points say
         const uint32_t th = ((uint32_t)layer >= a.small_layer && ef >= 64u) ? 0xFFFFFFFFu : layer >= 2 ? theta_top : theta;
+        PIPE_T(t_clear);
         __syncthreads();
         for (uint32_t i = tid; i < a.vis_words; i += NT) { L.ev[i] = 0u; L.ex[i] = 0u; }
-        if (tid == 0) { L.sh[CL_SH_NNEXT] = 0u; L.sh[CL_SH_NNEXT + 1] = 0u; L.sh[CL_SH_EVALS] = 0u; L.sh[CL_SH_EXPANDED] = 0u; L.sh[CL_SH_HAZARD] = 0u; }
+        if (tid == 0) {
+            L.sh[CL_SH_NNEXT] = 0u; L.sh[CL_SH_NNEXT + 1] = 0u; L.sh[CL_SH_EVALS] = 0u; L.sh[CL_SH_EXPANDED] = 0u; L.sh[CL_SH_HAZARD] = 0u;
+            *sh_minu = MDB_KEY_MAX; *sh_mine = MDB_KEY_MAX; L.sh[CL_SH_LT] = 0u; L.sh[CL_SH_LE] = 0u;   // (a layer may open with a single pop)
+        }
         __syncthreads();
         // ---- entry point: visited, evaluated (index.rs:219-231)
         const uint32_t k0 = rk_canon(tq[ep]);
@@ -192,12 +261,17 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
             cur[0] = ep;
         }
         __syncthreads();
+        PIPE_TE(CL_DBG_CLEAR, t_clear);
         uint32_t parity = 0u;
+        uint32_t ncert = ncur, npops = 0u;             // certain points evaluated so far (counted where they are discovered) | single pops of this layer
         for (uint32_t pass = 0; pass <= a.nu + 1u; ++pass) {     // every pass expands at least one point not expanded before
             if (pass > a.nu) { flagged = true; break; }
             // ---- whole frontiers at once: every point of `cur` is expanded by `gs` lanes, lane = edge slot
+            PIPE_T(t_rounds);
             while (ncur > 0u) {
+                PIPE_ACC(CL_DBG_NROUNDS, 1);
                 for (uint32_t base = 0; base < ncur; base += per) {
+                    PIPE_ACC(CL_DBG_NTRIPS, 1);
                     const uint32_t item = base + sub;
                     const bool act = item < ncur;
                     const uint32_t f = act ? cur[item] : 0u;
@@ -224,67 +298,79 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
                 }
                 __syncthreads();
                 ncur = L.sh[CL_SH_NNEXT + parity];
+                ncert += ncur;
                 const bool hz = L.sh[CL_SH_HAZARD] != 0u;
-                if (tid == 0) L.sh[CL_SH_NNEXT + (parity ^ 1u)] = 0u;   // (last read a round ago, behind that round's second barrier)
+                if (tid == 0) {
+                    L.sh[CL_SH_NNEXT + (parity ^ 1u)] = 0u;   // (last read a round ago, behind that round's second barrier)
+                    // the words of the next single pop (last read before the barrier that closed the pop before this round)
+                    *sh_minu = MDB_KEY_MAX; *sh_mine = MDB_KEY_MAX; L.sh[CL_SH_LT] = 0u; L.sh[CL_SH_LE] = 0u;
+                }
                 __syncthreads();
                 parity ^= 1u;
                 uint32_t* const t = cur; cur = nxt; nxt = t;
                 if (hz) { flagged = true; break; }
             }
+            PIPE_TE(CL_DBG_ROUNDS, t_rounds);
             if (flagged) break;
-            // ---- the one minimum unexpanded evaluated point, and the layer's nearest evaluated point so far
-            if (tid == 0) { *sh_minu = MDB_KEY_MAX; *sh_mine = MDB_KEY_MAX; L.sh[CL_SH_LT] = 0u; L.sh[CL_SH_LE] = 0u; }
-            __syncthreads();
-            {
-                uint64_t mu = MDB_KEY_MAX, me = MDB_KEY_MAX;
-                for (uint32_t w = tid; w < a.vis_words; w += NT) {
-                    uint32_t be = L.ev[w];
-                    const uint32_t bx = L.ex[w];
-                    while (be) {
-                        const uint32_t b = (uint32_t)__builtin_ctz(be);
-                        be &= be - 1u;
-                        const uint32_t c = 32u * w + b;
-                        const uint64_t kk = (uint64_t)rk_canon(tq[c]) << 32;
-                        me = min(me, kk | c);
-                        if (!((bx >> b) & 1u)) mu = min(mu, kk | (uint32_t)~c);
+            PIPE_T(t_pop);
+            // ---- ONE pass over the evaluated bitmap (`tpw` threads per word): the minimum pending point u with the pending points that
+            // tie with it, and the layer's nearest evaluated point so far
+            uint64_t mu = MDB_KEY_MAX, me = MDB_KEY_MAX;
+            uint32_t mties = 0u;                       // pending points of this thread at its own minimum image
+            for (uint32_t item = tid; item < (a.vis_words << ltpw); item += NT) {
+                const uint32_t w = item >> ltpw, b0 = (item & ((1u << ltpw) - 1u)) * wbits;
+                uint32_t be = (L.ev[w] >> b0) & wmask;
+                const uint32_t bx = L.ex[w] >> b0;
+                while (be) {
+                    const uint32_t b = (uint32_t)__builtin_ctz(be);
+                    be &= be - 1u;
+                    const uint32_t c = 32u * w + b0 + b;
+                    const uint32_t k32 = rk_canon(tq[c]);
+                    const uint64_t kk = (uint64_t)k32 << 32;
+                    me = min(me, kk | c);
+                    if (!((bx >> b) & 1u)) {
+                        const uint32_t mk = (uint32_t)(mu >> 32);
+                        mties = k32 < mk ? 1u : mties + (k32 == mk ? 1u : 0u);
+                        mu = min(mu, kk | (uint32_t)~c);
                     }
                 }
-                mu = cl_wave_min_u64(mu);
-                me = cl_wave_min_u64(me);
+            }
+            {
+                const uint64_t wmu = cl_wave_min_u64(mu), wme = cl_wave_min_u64(me);
                 if (lane == 0) {
-                    if (mu != MDB_KEY_MAX) atomicMin((unsigned long long*)sh_minu, (unsigned long long)mu);
-                    atomicMin((unsigned long long*)sh_mine, (unsigned long long)me);
+                    if (wmu != MDB_KEY_MAX) atomicMin((unsigned long long*)sh_minu, (unsigned long long)wmu);
+                    atomicMin((unsigned long long*)sh_mine, (unsigned long long)wme);
                 }
             }
             __syncthreads();
             const uint64_t ukey = *sh_minu;
             ep = (uint32_t)*sh_mine;                   // (smallest image, then smallest id: what the layer hands down, index.rs:177-181)
-            if (ukey == MDB_KEY_MAX) break;            // nothing pending: the layer is done
+            if (ukey == MDB_KEY_MAX) { PIPE_TE(CL_DBG_POPS, t_pop); break; }   // nothing pending: the layer is done
             const uint32_t du = (uint32_t)(ukey >> 32), u = ~(uint32_t)ukey;
-            // ---- the stop test by counting: evaluated points strictly closer than u, and no farther than u
-            {
-                uint32_t lt = 0u, le = 0u;
-                for (uint32_t w = tid; w < a.vis_words; w += NT) {
-                    uint32_t be = L.ev[w];
-                    while (be) {
-                        const uint32_t c = 32u * w + (uint32_t)__builtin_ctz(be);
-                        be &= be - 1u;
-                        const uint32_t kk = rk_canon(tq[c]);
-                        lt += kk < du ? 1u : 0u;
-                        le += kk <= du ? 1u : 0u;
-                    }
+            // ---- the stop test by counting, without a second pass (header: the counted stop test): what is closer than u is expanded —
+            // a certain point or an earlier single pop; what ties with u is pending (counted above) or an earlier single pop
+            if (mties && (uint32_t)(mu >> 32) == du) atomicAdd(&L.sh[CL_SH_LE], mties);
+            if (tid < 64) {                            // wave 0: the earlier single pops (two ballots per 64 of them)
+                uint32_t plt = 0u, ple = 0u;
+                for (uint32_t i0 = 0; i0 < npops; i0 += 64) {
+                    const bool have = i0 + lane < npops;
+                    const uint32_t pk = have ? L.hist[i0 + lane] : 0u;
+                    plt += (uint32_t)__popcll(__ballot(have && pk < du));
+                    ple += (uint32_t)__popcll(__ballot(have && pk <= du));
                 }
-                lt = cl_wave_sum(lt);
-                le = cl_wave_sum(le);
-                if (lane == 0 && le) { atomicAdd(&L.sh[CL_SH_LT], lt); atomicAdd(&L.sh[CL_SH_LE], le); }
+                if (lane == 0 && ple) { atomicAdd(&L.sh[CL_SH_LT], plt); atomicAdd(&L.sh[CL_SH_LE], ple); }
             }
             __syncthreads();
-            const uint32_t lt = L.sh[CL_SH_LT], le = L.sh[CL_SH_LE];
-            if (lt >= ef) break;                       // `distance > furthest.distance`: the layer is done (index.rs:246-248)
+            const uint32_t lt = ncert + L.sh[CL_SH_LT], le = ncert + L.sh[CL_SH_LE];
+            if (lt >= ef) { PIPE_TE(CL_DBG_POPS, t_pop); break; }   // `distance > furthest.distance`: the layer is done (index.rs:246-248)
             if (le - 1u >= ef) { flagged = true; break; }   // ef others no farther than u: its acceptance hung on the discovery order
-            if (tid == 0) cur[0] = u;
+            if (npops >= CL_POP_CAP) { flagged = true; break; }   // the list of this layer's single pops is full: the sequential form decides
+            if (tid == 0) { cur[0] = u; L.hist[npops] = du; }
+            ++npops;
             ncur = 1u;
             __syncthreads();
+            PIPE_TE(CL_DBG_POPS, t_pop);
+            PIPE_ACC(CL_DBG_NPOPS, 1);
         }
         if (flagged) break;
         evals += 1u + L.sh[CL_SH_EVALS];
@@ -300,9 +386,11 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
             a.fb[qi] = CL_FB_RERUN;
             if (!counted) atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
         }
+        CL_DBG_FLUSH();
         return true;
     }
     // ---- the hand-over (see upper_traverse_wave0)
+    PIPE_T(t_hand);
     if (a.vis_map) {
         // the next launch numbers the points differently (a superset): bit c -> bit vis_map[c]
         for (uint32_t i = tid; i < a.out_words; i += NT) L.vis_out[i] = 0u;
@@ -332,6 +420,8 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
             atomicAdd(&a.counters[1], (unsigned long long)expanded);
         }
     }
+    PIPE_TE(CL_DBG_HAND, t_hand);
+    CL_DBG_FLUSH();
     return false;
 }
 
@@ -353,14 +443,28 @@ __device__ void closure_bottom_block(const HnswUpArgs& a) {
         if (above == CL_FB_COUNT && threadIdx.x == 0) atomicAdd(&a.counters[MDB_CTR_CLOSURE_FALLBACKS], 1ull);
     }
     const ClLds L = cl_carve((uint32_t*)lds, a.vis_words, a.vis_map ? a.out_words : 0u);
+    const unsigned long long t_row = CL_DBG_NOW();
     const uint32_t* const tg = a.table + (size_t)qi * a.nu_pad;
     for (uint32_t i = threadIdx.x; i < a.vis_words; i += NT) L.vis[i] = a.in_vis ? a.in_vis[(size_t)qi * a.vis_words + i] : 0u;
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;             // of the row's images, taken from the registers the copy passes through
     if (a.cl_tlds) {
         const uint4* src = (const uint4*)tg;
         uint4* dst = (uint4*)L.row;
-        for (uint32_t i = threadIdx.x; i < a.nu_pad / 4; i += NT) dst[i] = src[i];
+        for (uint32_t i = threadIdx.x; i < a.nu_pad / 4; i += NT) {
+            const uint4 v = src[i];
+            dst[i] = v;
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t k = 4u * i + j < a.nu ? rk_canon(w[j]) : 0xFFFFFFFFu;   // (the padding behind the row's points is not a key)
+                mn = min(mn, k);
+                mx = 4u * i + j < a.nu ? max(mx, k) : mx;
+            }
+        }
     }
     __syncthreads();
-    if (a.cl_tlds) closure_traverse<NT>(a, qi, L, L.row);   // (two copies of the traversal: its lookups are ds_read in one, global loads in the other)
-    else closure_traverse<NT>(a, qi, L, tg);
+    const unsigned long long row_cycles = CL_DBG_NOW() - t_row;
+    // (two copies of the traversal: its lookups are ds_read in one, global loads in the other)
+    if (a.cl_tlds) closure_traverse<NT>(a, qi, L, L.row, true, mn, mx, row_cycles);
+    else closure_traverse<NT>(a, qi, L, tg, false, 0u, 0u, row_cycles);
 }

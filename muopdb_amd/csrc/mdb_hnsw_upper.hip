@@ -240,7 +240,8 @@ struct HnswUpArgs {
     int n16;
     const float* q;
     int qstride;
-    int dbg_on;               // MDB_PIPE_DBG builds: this launch adds its cycle sums to counters[4..15] (MDB_HNSW_DBG bit 0: bottom launch, bit 1: top)
+    int dbg_on;               // MDB_PIPE_DBG builds: this launch adds its cycle sums to counters[4..15] (MDB_HNSW_DBG bit 0: bottom launch, bit 1: top;
+                              // bit 2 / 3: the same two launches in the frontier form, CL_DBG_*)
     // frontier form (mdb_hnsw_closure.hip.h): fb[q] (CL_FB_*) = what is left to do for a query the form flagged; fb_role: what this
     // launch does with the word (CL_ROLE_*; nullptr / 0: no closure launch in this call)
     uint32_t* fb;
@@ -515,9 +516,11 @@ template <int METRIC, int N16>
 __device__ __forceinline__ bool closure_top_block(const HnswUpArgs& a, char* lds, const uint32_t*& row) {
     const ClLds L = cl_carve((uint32_t*)lds, a.vis_words, a.out_words);
     const int qi = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long t_row = CL_DBG_NOW();
     for (uint32_t i = threadIdx.x; i < a.vis_words; i += 256) L.vis[i] = 0u;
     // the block's own table row: one wave per tile of 64 points, thread = point (exact association, DPP-broadcast query chunks)
     const float* const ql = a.q + (size_t)qi * a.qstride + (lane & 15);
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;             // of the row's canonical images: the select's key range, taken where the row is made
     for (uint32_t tile = wave; tile < a.self_ntiles; tile += 4) {
         const float4* tp = a.self_tiles + (size_t)tile * (4 * N16) * MDB_TILE + lane;
         float acc[16];
@@ -533,11 +536,13 @@ __device__ __forceinline__ bool closure_top_block(const HnswUpArgs& a, char* lds
             t16_accumulate<METRIC>(acc, ql[16 * c], xv);
         }
         const uint32_t v = tile * MDB_TILE + lane;
-        L.row[v] = v < a.nu ? f32_orderable(finish_distance<METRIC>(__fadd_rn(0.0f, reduce_ordered<16>(acc)))) : SLOT_EMPTY;
+        const uint32_t img = v < a.nu ? f32_orderable(finish_distance<METRIC>(__fadd_rn(0.0f, reduce_ordered<16>(acc)))) : SLOT_EMPTY;
+        L.row[v] = img;
+        if (v < a.nu) { mn = min(mn, rk_canon(img)); mx = max(mx, rk_canon(img)); }
     }
     __syncthreads();
     row = L.row;
-    return closure_traverse<256>(a, qi, L, L.row);
+    return closure_traverse<256>(a, qi, L, L.row, true, mn, mx, CL_DBG_NOW() - t_row);
 }
 
 
@@ -683,6 +688,7 @@ static HnswUpArgs upper_args(mdb_ctx* ctx, const HnswUpper& up, const DistPlan& 
     }
     // MDB_PIPE_DBG builds (MDB_HNSW_DBG bit 0: the sequential bottom launch, bit 1: the sequential top launch)
     if (l.fb_role == CL_ROLE_NONE || l.fb_role == CL_ROLE_FALLBACK) a.dbg_on = (int)((ctx->opt.hnsw_dbg >> (top ? 1 : 0)) & 1);
+    else a.dbg_on = (int)((ctx->opt.hnsw_dbg >> (top ? 3 : 2)) & 1);
     if (l.fb_role != CL_ROLE_NONE) { a.fb = st + r.st_fb; a.fb_role = l.fb_role; }
     if (l.fb_role == CL_ROLE_BOTTOM || l.fb_role == CL_ROLE_SINGLE) {   // the frontier form's own theta over the TOP set
         if (up.nu2 > 0 && up.map21.p) { a.top_map = up.map21.p; a.top_n = up.nu2; }
