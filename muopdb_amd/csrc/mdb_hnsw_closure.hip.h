@@ -29,6 +29,20 @@
 // words (in `hist`, idle during the layers; wave 0 counts it).  `lt >= ef` and `le - 1 >= ef` mean what they meant.  A pop that finds
 // the list full flags the query: the sequential form is exact (tests/closure_bound_model.py restates this form and holds it against
 // closure_model.py's scan for every theta up to the exact one).
+// THE INCREMENTAL PASS.  Between two single pops of a layer the evaluated set only grows, and the pending set loses exactly one point:
+// the frontiers have run dry at a pop, so every certain point evaluated since the last pop is expanded by now and was never pending at
+// a pop; an uncertain point stays pending until it is the single pop itself.  Where every thread owns at most one slice of the bitmap
+// ((vis_words << ltpw) <= NT: up to 32 NT points — 8 k under the 256 threads of a top block, 32 k under the 1024 of the layer-1 block)
+// it keeps, across the pops of a layer, `seen` (the bits of its slice already folded), `mu` (its minimum pending key), `mties` (its
+// pending points at that image) and `me` (its minimum evaluated key), and a pop folds only ev & ~seen, skipping the expanded bits as
+// before.  The thread whose slice holds the popped u forgets the slice (seen = 0, mu = max, mties = 0) and walks it again at the next
+// pop, where u is expanded; ties of u in other threads' slices stay folded where they are.  So at every pop each thread's (mu, mties)
+// is the minimum and the tie count over the pending points of its slice and its `me` the minimum over the evaluated ones — what the
+// walk over the whole slice gives — and the block's u, lt, le, rows, counters and flags cannot depend on the change
+// (tests/closure_incremental_model.py restates the bookkeeping and holds every pop against the scan).  All four values start anew at
+// every layer: a layer that ends by lt >= ef leaves pending points behind, and they are not the next layer's.  With more slices
+// than threads every thread walks all of its slices at every pop, as before.  Only the layer's end needs the nearest evaluated point,
+// and `me` is a running minimum in either case (the evaluated set only grows): the block reduces it once, behind the layer's last pop.
 // What the counts cannot decide is an uncertain u that passes the strict test while ef OTHER evaluated points are no farther: whether
 // the reference ever accepted u depends on the discovery order.  That, and any evaluated NaN (whose flag the sequential kernels raise
 // where the reference panics), makes the query a FALLBACK: the block publishes nothing (its visited set is a copy in LDS) and the
@@ -225,6 +239,10 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
     uint32_t ltpw = 0u;
     while (ltpw < 5u && (a.vis_words << (ltpw + 1u)) <= (uint32_t)NT) ++ltpw;
     const uint32_t wbits = 32u >> ltpw, wmask = ltpw ? (1u << wbits) - 1u : 0xFFFFFFFFu;
+    // every thread owns at most one slice (up to 32 NT points: both launches of the split path on the bench, 31 k and 1 k points):
+    // the pass is incremental
+    const bool own_one = (a.vis_words << ltpw) <= (uint32_t)NT;
+    const uint32_t own_w = (uint32_t)tid >> ltpw, own_b0 = ((uint32_t)tid & ((1u << ltpw) - 1u)) * wbits;
     uint64_t* const sh_minu = (uint64_t*)(L.sh + CL_SH_MINU);
     uint64_t* const sh_mine = (uint64_t*)(L.sh + CL_SH_MINE);
     PIPE_T(t_theta);
@@ -264,6 +282,10 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
         PIPE_TE(CL_DBG_CLEAR, t_clear);
         uint32_t parity = 0u;
         uint32_t ncert = ncur, npops = 0u;             // certain points evaluated so far (counted where they are discovered) | single pops of this layer
+        // the single pops' pass, per thread and per layer (header: the incremental pass): bits of its slice already folded | minimum
+        // pending key (image, ~id) | pending points at that image | minimum evaluated key (image, id)
+        uint32_t seen = 0u, mties = 0u;
+        uint64_t mu = MDB_KEY_MAX, me = MDB_KEY_MAX;
         for (uint32_t pass = 0; pass <= a.nu + 1u; ++pass) {     // every pass expands at least one point not expanded before
             if (pass > a.nu) { flagged = true; break; }
             // ---- whole frontiers at once: every point of `cur` is expanded by `gs` lanes, lane = edge slot
@@ -314,13 +336,10 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
             if (flagged) break;
             PIPE_T(t_pop);
             // ---- ONE pass over the evaluated bitmap (`tpw` threads per word): the minimum pending point u with the pending points that
-            // tie with it, and the layer's nearest evaluated point so far
-            uint64_t mu = MDB_KEY_MAX, me = MDB_KEY_MAX;
-            uint32_t mties = 0u;                       // pending points of this thread at its own minimum image
-            for (uint32_t item = tid; item < (a.vis_words << ltpw); item += NT) {
-                const uint32_t w = item >> ltpw, b0 = (item & ((1u << ltpw) - 1u)) * wbits;
-                uint32_t be = (L.ev[w] >> b0) & wmask;
-                const uint32_t bx = L.ex[w] >> b0;
+            // tie with it; the layer's nearest evaluated point so far stays in the threads' `me`
+            // the bits `be` of the slice at bit b0 of word w (bx: the expanded bitmap, shifted alike): every point into me, the pending ones
+            // into mu and mties (pending points of this thread at its own minimum image)
+            const auto fold = [&](const uint32_t w, const uint32_t b0, uint32_t be, const uint32_t bx) {
                 while (be) {
                     const uint32_t b = (uint32_t)__builtin_ctz(be);
                     be &= be - 1u;
@@ -334,17 +353,26 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
                         mu = min(mu, kk | (uint32_t)~c);
                     }
                 }
+            };
+            if (own_one) {                             // (block-uniform) only the bits evaluated since this thread's last walk
+                if ((uint32_t)tid < (a.vis_words << ltpw)) {
+                    const uint32_t be = ((L.ev[own_w] >> own_b0) & wmask) & ~seen;
+                    seen |= be;
+                    fold(own_w, own_b0, be, L.ex[own_w] >> own_b0);
+                }
+            } else {                                   // several slices per thread: all of them, from nothing
+                mu = MDB_KEY_MAX; mties = 0u;        // (me runs on: the evaluated set only grows)
+                for (uint32_t item = tid; item < (a.vis_words << ltpw); item += NT) {
+                    const uint32_t w = item >> ltpw, b0 = (item & ((1u << ltpw) - 1u)) * wbits;
+                    fold(w, b0, (L.ev[w] >> b0) & wmask, L.ex[w] >> b0);
+                }
             }
             {
-                const uint64_t wmu = cl_wave_min_u64(mu), wme = cl_wave_min_u64(me);
-                if (lane == 0) {
-                    if (wmu != MDB_KEY_MAX) atomicMin((unsigned long long*)sh_minu, (unsigned long long)wmu);
-                    atomicMin((unsigned long long*)sh_mine, (unsigned long long)wme);
-                }
+                const uint64_t wmu = cl_wave_min_u64(mu);     // (me is a running minimum: reduced once, behind the layer's last pop)
+                if (lane == 0 && wmu != MDB_KEY_MAX) atomicMin((unsigned long long*)sh_minu, (unsigned long long)wmu);
             }
             __syncthreads();
             const uint64_t ukey = *sh_minu;
-            ep = (uint32_t)*sh_mine;                   // (smallest image, then smallest id: what the layer hands down, index.rs:177-181)
             if (ukey == MDB_KEY_MAX) { PIPE_TE(CL_DBG_POPS, t_pop); break; }   // nothing pending: the layer is done
             const uint32_t du = (uint32_t)(ukey >> 32), u = ~(uint32_t)ukey;
             // ---- the stop test by counting, without a second pass (header: the counted stop test): what is closer than u is expanded —
@@ -366,6 +394,8 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
             if (le - 1u >= ef) { flagged = true; break; }   // ef others no farther than u: its acceptance hung on the discovery order
             if (npops >= CL_POP_CAP) { flagged = true; break; }   // the list of this layer's single pops is full: the sequential form decides
             if (tid == 0) { cur[0] = u; L.hist[npops] = du; }
+            // u leaves the pending set: the thread that folded it forgets its slice and walks it again at the next pop
+            if (own_one && (uint32_t)tid == ((u >> 5) << ltpw) + ((u & 31u) >> (5u - ltpw))) { seen = 0u; mu = MDB_KEY_MAX; mties = 0u; }
             ++npops;
             ncur = 1u;
             __syncthreads();
@@ -373,6 +403,13 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
             PIPE_ACC(CL_DBG_NPOPS, 1);
         }
         if (flagged) break;
+        {   // the layer's nearest evaluated point (smallest image, then smallest id: what the layer hands down, index.rs:177-181); the word
+            // is still at its reset value: no pop writes it
+            const uint64_t wme = cl_wave_min_u64(me);
+            if (lane == 0) atomicMin((unsigned long long*)sh_mine, (unsigned long long)wme);
+            __syncthreads();
+            ep = (uint32_t)*sh_mine;
+        }
         evals += 1u + L.sh[CL_SH_EVALS];
         expanded += L.sh[CL_SH_EXPANDED];
     }
