@@ -282,11 +282,18 @@ mdb_status mdb_ivf_coarse_keys(mdb_ivf* ivf, const float* queries, size_t b, siz
 mdb_status mdb_ivf_merge_coarse_keys(mdb_ivf* ivf, const uint64_t* keys, size_t b, size_t parts, size_t num_probes, mdb_mem mem,
                                      uint32_t* probes_out);
 /* BlockBasedIvf::search :396-413 (probes == NULL) or search_with_centroids_and_remap :298-332
- * (probes = [B][num_probes] centroid ids).  Results ordered by IdWithScore (score, doc_id). */
+ * (probes = [B][num_probes] centroid ids).  Results ordered by IdWithScore (score, doc_id).
+ * A caller-given probe table is taken as the reference takes any Vec<usize> (index.rs:250-286): it may name lists in any order
+ * and more than once, and EVERY occurrence is scanned — a list named m times offers each of its points m times, and a row can
+ * hold the same doc id m times with one score (no dedup).  A list id >= num_clusters is MDB_ERR_FORMAT for the call (the
+ * reference's Err("Index out of bound"), storage.rs:280-286): the list is never read, the outputs of the failed call are
+ * unspecified, the handle serves the next call.  The ids are checked on the device, so an MDB_MEM_DEVICE call returns MDB_OK and
+ * the error is deferred to mdb_sync (once); mdb_ivf_search_submit reports it from mdb_wait. */
 mdb_status mdb_ivf_search(mdb_ivf* ivf, const float* queries, size_t b, const uint32_t* probes, size_t num_probes,
                           size_t k, mdb_mem mem, mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out);
 /* same, stopping before the doc-id remap: the top-k by (distance, point id) —
- * BlockBasedIvf::search_with_centroids :250-286 (the sharded multi-GPU path uses the block form, mdb_ivf_search_shard) */
+ * BlockBasedIvf::search_with_centroids :250-286 (the sharded multi-GPU path uses the block form, mdb_ivf_search_shard).
+ * Caller-given probe tables: as for mdb_ivf_search (any order, repeats scanned again, an id >= num_clusters is MDB_ERR_FORMAT). */
 mdb_status mdb_ivf_search_points(mdb_ivf* ivf, const float* queries, size_t b, const uint32_t* probes,
                                  size_t num_probes, size_t k, mdb_mem mem, uint32_t* point_ids_out, float* scores_out,
                                  uint32_t* counts_out);
@@ -299,7 +306,9 @@ mdb_status mdb_ivf_search_points(mdb_ivf* ivf, const float* queries, size_t b, c
  * every query, otherwise at least b bitmaps (one per query, [n_bitmaps][words_per_bitmap] u32), each of words_per_bitmap >=
  * ceil(num_vectors / 32) words — anything shorter is MDB_ERR_INVALID_ARG, never an out-of-bounds read.  Filtered points are
  * skipped BEFORE the distance (the reference drops them after it).  Two host threads with different filters on handles over one
- * index do not interact.  (The stateful mdb_*_set_filter entries of rounds 1-3 are gone: one way to pass a planner.) */
+ * index do not interact.  (The stateful mdb_*_set_filter entries of rounds 1-3 are gone: one way to pass a planner.)
+ * Caller-given probe tables: as for mdb_ivf_search — every occurrence of a list is scanned, so an allowed point of a list named
+ * m times is returned m times; an id >= num_clusters is MDB_ERR_FORMAT. */
 mdb_status mdb_ivf_search_filtered(mdb_ivf* ivf, const float* queries, size_t b, const uint32_t* probes, size_t num_probes, size_t k,
                                    mdb_mem mem, const uint32_t* allow, size_t n_bitmaps, size_t words_per_bitmap,
                                    mdb_u128* doc_ids_out, float* scores_out, uint32_t* counts_out);
@@ -311,7 +320,8 @@ mdb_status mdb_ivf_attach(mdb_ctx* ctx, mdb_ivf* src, mdb_ivf** out);
 /* Asynchronous host-buffer call for hosts that overlap batches (a tokio task per batch): returns once the copies and
  * kernels are ENQUEUED on the handle's context; queries / probes / bitmaps may be reused at once, the output buffers are
  * filled by mdb_wait(ctx), which also reports the deferred status (MDB_ERR_NAN ...).  One pending call per context —
- * keep several in flight with one context + attached handle each.  mdb_poll(ctx) != 0 when mdb_wait would not block. */
+ * keep several in flight with one context + attached handle each.  mdb_poll(ctx) != 0 when mdb_wait would not block.
+ * Caller-given probe tables: as for mdb_ivf_search; a list id >= num_clusters is reported by mdb_wait as MDB_ERR_FORMAT. */
 mdb_status mdb_ivf_search_submit(mdb_ivf* ivf, const float* queries, size_t b, const uint32_t* probes, size_t num_probes, size_t k,
                                  const uint32_t* allow, size_t n_bitmaps, size_t words_per_bitmap, mdb_u128* doc_ids_out,
                                  float* scores_out, uint32_t* counts_out);
@@ -469,7 +479,10 @@ mdb_status mdb_multi_spann_replay_invalidations(mdb_multi_spann* ms, const void*
  *   3. mdb_*_merge_shards on every rank (device buffers): the k smallest of the union by (distance, point id), then doc ids
  *      from the handle's replicated table, ordered by IdWithScore (score, doc_id).
  * The result equals the unsharded mdb_*_search row for row, including ties at rank k under non-monotone doc ids
- * (reindexed segments) and duplicate PQ codes.  The role replaced: rs/aggregator/src/aggregator.rs:80-135. */
+ * (reindexed segments) and duplicate PQ codes.  The role replaced: rs/aggregator/src/aggregator.rs:80-135.
+ * A caller-given probe table (mdb_ivf_search_shard with probes != NULL: the merged coarse keys, or another process's rows) follows
+ * the contract stated at mdb_ivf_search: any order, a list named m times is scanned m times by the rank that owns it, and an id
+ * >= num_clusters is MDB_ERR_FORMAT on EVERY rank, whichever rank would have owned it (deferred to mdb_sync for MDB_MEM_DEVICE). */
 size_t mdb_points_block_bytes(size_t b, size_t k);
 mdb_status mdb_points_block_views(void* block, size_t b, size_t k, uint32_t** point_ids, float** scores, uint32_t** counts,
                                   uint8_t** found);

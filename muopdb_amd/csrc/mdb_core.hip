@@ -31,7 +31,7 @@ mdb_status mdb_scratch(mdb_ctx* ctx, size_t bytes, void** out) {
 static mdb_status flags_to_status(mdb_ctx* ctx, uint32_t f) {
     if (f & MDB_FLAG_NAN) return mdb_fail(ctx, MDB_ERR_NAN, "a distance evaluated to NaN (reference: NotNan::new(..).unwrap() panics)");
     if (f & MDB_FLAG_OVERFLOW) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "traversal state exceeded the on-chip capacity");
-    if (f & MDB_FLAG_RANGE) return mdb_fail(ctx, MDB_ERR_FORMAT, "index refers to a point id outside the vector storage");
+    if (f & MDB_FLAG_RANGE) return mdb_fail(ctx, MDB_ERR_FORMAT, "a probe table names a posting list >= num_clusters, or the index refers to a point id outside the vector storage");
     return MDB_OK;
 }
 

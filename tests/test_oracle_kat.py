@@ -654,3 +654,38 @@ def test_reassigned_ids_product_equals_oracle_on_random_lists(oracle):
         assert [int(x) for x in B.reassigned_ids(lists, n)] == want
         valid = sorted(x for x in want if x >= 0)
         assert valid == list(range(len(valid)))                          # a permutation of 0 .. n' - 1
+
+
+# ----------------------------------------------------------------------------- caller-given probe tables
+@pytest.mark.parametrize("metric", ["l2", "dot"])
+@pytest.mark.parametrize("kind", ["f32", "pq"])
+def test_probe_tables_are_the_concatenation_of_their_columns(oracle, kind, metric):
+    """rs/index/src/ivf/block_based/index.rs:250-286 restated without the heap: search_with_centroids over any table of list ids is
+    the k smallest of the per-column results laid end to end — a list named m times contributes its points m times, in any column
+    order.  With monotone doc ids (100 + 3 i) the (distance, point id) and (score, doc id) orders coincide, so ties at rank k are
+    decided identically.  The worlds and tables are those of tests/test_gpu_probe_tables.py."""
+    from tests.test_gpu_probe_tables import B, NLISTS, build_world
+    w = build_world(oracle, kind, lambda n: [100 + 3 * i for i in range(n)])
+    o, q, sizes = w["o_" + metric], w["q"], w["sizes"]
+    per = []                                                             # every list on its own: (doc ids, scores) per query
+    for c in range(NLISTS):
+        r = o.search(q, max(sizes[c], 1), probes=np.full((B, 1), c, np.uint32))
+        assert np.all(r.counts == sizes[c]) and not r.hi[:, :sizes[c]].any()
+        per.append((r.lo[:, :sizes[c]].copy(), r.scores[:, :sizes[c]].copy()))
+    for name, table in w["tables"].items():
+        got = {k: o.search(q, k, probes=table, threads=8) for k in (1, 10, 2000)}
+        for i in range(B):
+            # the concatenation's order by (score, doc id): the lists' entries, each repeated once per column that names its list
+            times = np.bincount(table[i], minlength=NLISTS)
+            docs, sc = np.concatenate([p[0][i] for p in per]), np.concatenate([p[1][i] for p in per])
+            reps = np.repeat(times, sizes)
+            order = np.lexsort((docs, sc))
+            docs, sc = np.repeat(docs[order], reps[order]), np.repeat(sc[order], reps[order])
+            assert len(docs) == sum(sizes[c] for c in table[i])
+            for k, r in got.items():
+                n = min(k, len(docs))
+                assert int(r.counts[i]) == n, (name, k, i)
+                assert np.array_equal(r.lo[i, :n], docs[:n]) and not r.hi[i, :n].any(), (name, k, i)
+                assert np.array_equal(r.scores[i, :n].view(np.uint32), sc[:n].view(np.uint32)), (name, k, i)
+    with pytest.raises(ValueError):                                      # storage.rs:280-286: Err("Index out of bound")
+        o.search(q, 10, probes=np.full((B, 1), NLISTS, np.uint32))
