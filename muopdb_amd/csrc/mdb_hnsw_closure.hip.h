@@ -3,9 +3,11 @@
 //
 // Every distance a layer >= 1 can ask for is in the table row T[q][.] before its traversal starts, and everything the layer hands on
 // is a union, a count or a minimum: the visited set, the evaluations (points newly visited), the expansions (expanded points with a
-// non-empty row) and the nearest evaluated point.  Let theta be NO LARGER than the ef-th smallest canonical image of the row (index
-// ef - 1 of the sorted row; +inf for a set of <= ef points; cl_theta takes a histogram bin's lower edge) and call a point CERTAIN when
-// d < theta.  At most ef - 2 other points are as near as a certain point c, so
+// non-empty row) and the nearest evaluated point.  A layer evaluates its entry point and the points it discovers that NO LAYER ABOVE
+// HAS VISITED (the reference keeps one visited set per ann_search, shared by all layers; W and the candidates are per layer): its POOL
+// is (the layer's points \ visited on entry) + {entry point}.  Let theta be NO LARGER than the ef-th smallest canonical image of the
+// pool (index ef - 1 of the sorted pool; +inf for a pool of <= ef points) and call a point CERTAIN when d < theta.  At most ef - 2
+// other points THAT THIS LAYER CAN EVALUATE are as near as a certain point c, so
 //   * c is accepted whenever it is discovered (`|W| < ef or d < furthest` cannot fail), and is never evicted;
 //   * the `distance > furthest` break cannot fire when c is popped, nor on anything popped while c is pending (the minimum
 //     candidate is no farther than c).
@@ -14,10 +16,21 @@
 // evaluated point u (smallest image, largest id among ties: the candidates heap's order) and restates the reference's stop test as
 // counts over the evaluated set: #{d < d_u} >= ef: the layer is done; else u is expanded alone and the rounds resume.  Points the
 // reference rejected at discovery stay in the evaluated set as pseudo-candidates: when one becomes the minimum it fails the count,
-// and so does every true candidate behind it.  theta of a SUPERSET of the layer's points is no larger than the layer's own, so it is
+// and so does every true candidate behind it.  theta of a SUPERSET of the pool is no larger than the pool's own, so it is
 // valid too, only less useful: one select over the launch's row serves its lowest layer, one over the TOP set the layers >= 2 (the
 // split path's top launch numbers exactly that set; a launch over every upper layer reaches it through map21).
 // hnsw_upper_kernel's closure of a layer of <= 64 points is the special case theta = +inf.
+// THE POOL.  cl_theta gets the block's visited bitmap and skips every key whose bit is set, in both passes.
+// A select runs LATE: at the first layer that uses it, behind that layer's entry into L.vis, so the layers above have left their visits there — and the layer's own entry point
+// too, which the select therefore leaves out: it takes index ef - 2 (the (ef - 1)-th smallest) of the unvisited REST.  With the entry
+// point put back that value sits at index ef - 2 or ef - 1 of the pool: never above the pool's index ef - 1, one rank conservative
+// when the entry point is farther than it.  A rest of <= ef - 1 points is a pool of <= ef: +inf (the first pass's grand total is the
+// rest's size).  A select is REUSED by every lower layer of the launch that uses the same set: the visited set only grows, and a lower
+// layer's entry point was evaluated by the layer above it — unvisited, or the entry point, when the select ran — so every lower pool
+// is a subset of rest + {that one point}, whose index ef - 1 is no smaller than the rest's index ef - 2.  On the bench the layers
+// above hand layer 1 ~810 of the 977 TOP points, some six of them below the row's theta: each cost the select over the row a rank and
+// the block a single pop (tests/closure_visited_model.py restates pool, rank, late select and reuse and holds chains of layers
+// against closure_model.search_layer; tests/test_gpu_hnsw_closure_visited.py).
 // THE COUNTED STOP TEST.  A single pop happens when the frontiers have run dry: every certain point discovered so far is expanded, so
 // every pending (evaluated, unexpanded) point is uncertain and u is the nearest of them.  An evaluated point closer than u is not
 // pending, hence expanded: a certain point (d < theta <= d_u) or an earlier single pop of this layer.  So
@@ -80,7 +93,10 @@
 #define CL_SH_MINU 12            // u64: min (image, ~id) over evaluated and unexpanded
 #define CL_SH_MINE 14            // u64: min (image, id) over evaluated
 #define CL_SH_FLAGGED 16         // how closure_traverse ended, for its caller
-#define CL_POP_CAP 256u          // single pops of one layer whose images the block keeps (bench: 8 per block on layer 1, 5 in the top block)
+#define CL_SH_ROWMIN 17          // smallest and largest canonical image of the row, where the caller took them while it made the row
+#define CL_SH_ROWMAX 18
+static_assert(CL_SH_ROWMAX < CL_SH_WORDS, "the block's shared words");
+#define CL_POP_CAP 256u          // single pops of one layer whose images the block keeps (bench: 3.4 per block on layer 1, 1 in the top block)
 // MDB_PIPE_DBG builds (mdb_hnsw_dev.hip.h), MDB_HNSW_DBG bit 2: the layer-1 launch, bit 3: the top launch — thread 0's cycle / event sums of the
 // frontier form per call (a batch), in counters[5..15] (word 4 is the fallback counter):
 //   row copy or evaluation | theta (both selects) | per layer: clear + entry point | rounds | trips inside them (count) | rounds (count) |
@@ -131,9 +147,12 @@ __device__ __forceinline__ uint64_t cl_wave_min_u64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// theta: a LOWER BOUND of the canonical image at index ef - 1 of the sorted keys[0 .. n) (0xFFFFFFFF = +inf when n <= ef) — the lower edge
-// of the histogram bin that holds that index after at most two block-wide passes of up to 11 bits each, most significant bits first,
-// over the bits the row's key range has.  Exact for a range below 2^22 images, else the bin is 2^(range bits - 22) images wide.
+// theta: a LOWER BOUND of the canonical image at index ef - 2 of the sorted keys[0 .. n) WHOSE BIT IN `vis` IS CLEAR (header: THE POOL;
+// `vis` in the numbering of `keys`, the caller's entry point marked in it; 0xFFFFFFFF = +inf when n <= ef or when ef - 1 keys or fewer
+// are left; 0 for ef < 2: no such index) — the lower edge of the histogram bin that holds that index after at most two block-wide
+// passes of up to 11 bits each, most significant bits first, over the bits the row's key range has (the range of ALL n keys: a range
+// over a superset is still a range; keys that are all one image give that image, whatever is left).  Exact for a range below 2^22
+// images, else the bin is 2^(range bits - 22) images wide.
 // What the header derives from theta is all derived from "at most ef - 2 other points are as near as a point with d < theta", which
 // holds for every value up to the exact one.  A point between the bound and the exact value is uncertain instead of certain: it is
 // popped alone, where the counts let it through (lt <= ef - 2) and cannot flag it (le - 1 <= ef - 2), and expanded as it would have
@@ -142,35 +161,41 @@ __device__ __forceinline__ uint64_t cl_wave_min_u64(uint64_t v) {
 // The histogram is `hist` and the two frontier lists behind it (idle outside the layers): CL_TH_WORDS = 2048 counters, one per digit;
 // wave 0 scans the sums of 256 groups of 8, then the 8 words of the group that holds the index.  A pass is a block-wide scan of the
 // keys with one LDS add per key: its cost is the passes times the keys per thread, which is why there are two and not five.
-// have_mm: the caller folded the keys' minimum and maximum into the pass that produced the row (mn, mx: this thread's share).
-// Called by every thread.
+// have_mm: the keys' minimum and maximum are in sh[CL_SH_ROWMIN / _ROWMAX] (closure_traverse puts them there at its entry, from what
+// the caller folded into the pass that produced the row).  Called by every thread.
 #define CL_TH_WORDS (CL_SUBHIST * 256 + 2 * CL_FR_CAP)
 static_assert(CL_TH_WORDS == 2048 && CL_TH_WORDS % 4 == 0, "cl_theta: 256 groups of 8 words, cleared with 16-byte stores");
 static_assert(CL_POP_CAP <= CL_SUBHIST * 256, "the single pops' images live in hist");
 template <int NT>
 __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ idx, const uint32_t n, const uint32_t ef,
-                                             uint32_t* hist, uint32_t* sh, const bool have_mm, uint32_t mn, uint32_t mx) {
+                                             const uint32_t* vis, uint32_t* hist, uint32_t* sh, const bool have_mm) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (n <= ef) return 0xFFFFFFFFu;
-    if (tid == 0) { sh[CL_SH_KMIN] = 0xFFFFFFFFu; sh[CL_SH_KMAX] = 0u; }
+    if (ef < 2u) return 0u;                            // (no rank ef - 2: nothing is certain, every point is popped alone)
+    uint32_t kmin, range;
+    if (!have_mm && tid == 0) { sh[CL_SH_KMIN] = 0xFFFFFFFFu; sh[CL_SH_KMAX] = 0u; }
     for (int i = tid; i < CL_TH_WORDS / 4; i += NT) ((uint4*)hist)[i] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
-    if (!have_mm) {
-        mn = 0xFFFFFFFFu; mx = 0u;
+    if (have_mm) {                                     // closure_traverse reduced the caller's shares at its entry
+        kmin = sh[CL_SH_ROWMIN];
+        range = sh[CL_SH_ROWMAX] - kmin;
+    } else {                                           // over the whole set: a range over a superset of the pool is still a range
+        uint32_t mn = 0xFFFFFFFFu, mx = 0u;
         for (uint32_t i = tid; i < n; i += NT) {
             const uint32_t k = rk_canon(keys[idx ? idx[i] : i]);
             mn = min(mn, k);
             mx = max(mx, k);
         }
+        mn = wave_min_u32(mn);
+        mx = wave_max_u32(mx);
+        if (lane == 0) { atomicMin(&sh[CL_SH_KMIN], mn); atomicMax(&sh[CL_SH_KMAX], mx); }
+        __syncthreads();
+        kmin = sh[CL_SH_KMIN];
+        range = sh[CL_SH_KMAX] - kmin;
     }
-    mn = wave_min_u32(mn);
-    mx = wave_max_u32(mx);
-    if (lane == 0) { atomicMin(&sh[CL_SH_KMIN], mn); atomicMax(&sh[CL_SH_KMAX], mx); }
-    __syncthreads();
-    const uint32_t kmin = sh[CL_SH_KMIN], range = sh[CL_SH_KMAX] - kmin;
     int hi = range ? 32 - __builtin_clz(range) : 0;   // bits [lo, hi) are decided by the next pass; the bits above them equal `prefix`
-    if (hi == 0) __syncthreads();                      // (no pass: the words just read are written again by the next select)
-    uint32_t prefix = 0u, k = ef - 1u;
+    if (hi == 0 && !have_mm) __syncthreads();          // (no pass: the words just read are written again by the next select)
+    uint32_t prefix = 0u, k = ef - 2u;
     for (int pass = 0; pass < 2 && hi > 0; ++pass) {   // (uniform)
         const int bits = min(hi, 11), lo = hi - bits;
         const uint32_t dmask = (1u << bits) - 1u;
@@ -179,7 +204,9 @@ __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, 
             __syncthreads();
         }
         for (uint32_t i = tid; i < n; i += NT) {
-            const uint32_t kp = rk_canon(keys[idx ? idx[i] : i]) - kmin;
+            const uint32_t c = idx ? idx[i] : i;
+            if ((vis[c >> 5] >> (c & 31)) & 1u) continue;   // visited on a layer above (or this layer's entry point): not in the pool
+            const uint32_t kp = rk_canon(keys[c]) - kmin;
             const uint32_t above = hi >= 32 ? 0u : kp >> hi;
             if (above == prefix) atomicAdd(&hist[(kp >> lo) & dmask], 1u);
         }
@@ -199,7 +226,11 @@ __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, 
                 if (lane >= o) inc += t;
             }
             uint32_t before = inc - tot;
-            if (before <= k && k < inc) {              // exactly one lane
+            // the first pass's grand total is the pool's size: ef - 1 unvisited points or fewer leave the layer <= ef points to evaluate
+            const uint32_t pool = (uint32_t)__shfl((int)inc, 63, 64);
+            if (pass == 0 && pool <= ef - 1u) {
+                if (lane == 0) sh[CL_SH_DIGIT] = 0xFFFFFFFFu;
+            } else if (before <= k && k < inc) {       // exactly one lane
                 int j = 0;
                 while (j < 3 && before + c[j] <= k) { before += c[j]; ++j; }
                 const uint32_t* const g = hist + 8u * (4u * lane + j);   // the word inside the group
@@ -210,7 +241,9 @@ __device__ __forceinline__ uint32_t cl_theta(const uint32_t* __restrict__ keys, 
             }
         }
         __syncthreads();
-        prefix = (prefix << bits) | sh[CL_SH_DIGIT];
+        const uint32_t digit = sh[CL_SH_DIGIT];
+        if (digit == 0xFFFFFFFFu) return 0xFFFFFFFFu;  // (block-uniform; the word is next written behind the next select's barriers)
+        prefix = (prefix << bits) | digit;
         k = sh[CL_SH_K];
         hi = lo;
     }
@@ -245,12 +278,18 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
     const uint32_t own_w = (uint32_t)tid >> ltpw, own_b0 = ((uint32_t)tid & ((1u << ltpw) - 1u)) * wbits;
     uint64_t* const sh_minu = (uint64_t*)(L.sh + CL_SH_MINU);
     uint64_t* const sh_mine = (uint64_t*)(L.sh + CL_SH_MINE);
-    PIPE_T(t_theta);
-    const uint32_t theta = cl_theta<NT>(tq, nullptr, a.nu, ef, L.hist, L.sh, have_mm, mn, mx);
-    // one launch over every upper layer: the layers >= 2 hold the TOP set only, and theta of the whole row would leave next to none of
-    // its points certain (the layer would be popped one point at a time)
-    const uint32_t theta_top = (a.top_map && a.layer_hi >= 2) ? cl_theta<NT>(tq, a.top_map, a.top_n, ef, L.hist, L.sh, false, 0u, 0u) : theta;
-    PIPE_TE(CL_DBG_THETA, t_theta);
+    // the selects run late (header: THE POOL): each at the first layer that uses it, behind that layer's entry into L.vis.  The caller's
+    // shares of the row's key range are reduced here, so that no thread carries them through the layers above
+    if (have_mm) {
+        if (tid == 0) { L.sh[CL_SH_ROWMIN] = 0xFFFFFFFFu; L.sh[CL_SH_ROWMAX] = 0u; }
+        __syncthreads();
+        const uint32_t wmn = wave_min_u32(mn), wmx = wave_max_u32(mx);
+        if (lane == 0) { atomicMin(&L.sh[CL_SH_ROWMIN], wmn); atomicMax(&L.sh[CL_SH_ROWMAX], wmx); }   // (read behind the first layer's barriers)
+    }
+    // theta: over the launch's row; theta_top: one launch over every upper layer — the layers >= 2 hold the TOP set only, and theta of
+    // the whole row would leave next to none of its points certain (the layer would be popped one point at a time)
+    uint32_t theta = 0u, theta_top = 0u;
+    bool have_theta = false, have_top = false;
     uint32_t ep = a.in_ep ? a.in_ep[qi] : a.entry_c;
     uint32_t evals = a.in_cnt ? a.in_cnt[4 * qi + 0] : 0u, expanded = a.in_cnt ? a.in_cnt[4 * qi + 1] : 0u;
     bool flagged = (a.in_cnt && a.in_cnt[4 * qi + 2]) || (a.in_ovf && a.in_ovf[qi] != 0u) || ep >= a.nu;
@@ -260,7 +299,8 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
     for (int layer = a.layer_hi; layer >= a.layer_lo && !flagged; --layer) {
         const uint32_t* const lrows = a.rows + (size_t)(layer - a.row_layer0) * a.nu * su;
         // a layer of <= 64 points with edges only among them (ef >= 64): all of it is certain, whatever the row's other points say
-        const uint32_t th = ((uint32_t)layer >= a.small_layer && ef >= 64u) ? 0xFFFFFFFFu : layer >= 2 ? theta_top : theta;
+        const bool all_certain = (uint32_t)layer >= a.small_layer && ef >= 64u;
+        const bool use_top = layer >= 2 && a.top_map != nullptr;
         PIPE_T(t_clear);
         __syncthreads();
         for (uint32_t i = tid; i < a.vis_words; i += NT) { L.ev[i] = 0u; L.ex[i] = 0u; }
@@ -272,7 +312,6 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
         // ---- entry point: visited, evaluated (index.rs:219-231)
         const uint32_t k0 = rk_canon(tq[ep]);
         if (k0 == RK_NAN_KEY) { flagged = true; break; }
-        uint32_t ncur = k0 < th ? 1u : 0u;
         if (tid == 0) {
             L.vis[ep >> 5] |= 1u << (ep & 31);
             L.ev[ep >> 5] |= 1u << (ep & 31);
@@ -280,6 +319,18 @@ __device__ __forceinline__ bool closure_traverse(const HnswUpArgs& a, const int 
         }
         __syncthreads();
         PIPE_TE(CL_DBG_CLEAR, t_clear);
+        // ---- this layer's theta: a select taken at a layer above over the same set serves (the visited set has only grown since, and
+        // this entry point was unvisited, or the entry point, when it ran); else it runs now, over the points L.vis leaves
+        if (!all_certain && !(use_top ? have_top : have_theta)) {   // (block-uniform)
+            PIPE_T(t_theta);
+            if (use_top) { theta_top = cl_theta<NT>(tq, a.top_map, a.top_n, ef, L.vis, L.hist, L.sh, false); have_top = true; }
+            else { theta = cl_theta<NT>(tq, nullptr, a.nu, ef, L.vis, L.hist, L.sh, have_mm); have_theta = true; }
+            if (tid == 0) cur[0] = ep;                 // (the histogram lay over the frontier lists)
+            __syncthreads();
+            PIPE_TE(CL_DBG_THETA, t_theta);
+        }
+        const uint32_t th = all_certain ? 0xFFFFFFFFu : use_top ? theta_top : theta;
+        uint32_t ncur = k0 < th ? 1u : 0u;
         uint32_t parity = 0u;
         uint32_t ncert = ncur, npops = 0u;             // certain points evaluated so far (counted where they are discovered) | single pops of this layer
         // the single pops' pass, per thread and per layer (header: the incremental pass): bits of its slice already folded | minimum
