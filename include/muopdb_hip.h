@@ -88,7 +88,43 @@ typedef struct {
     uint64_t ivf_pq_codebook_offset, ivf_pq_codebook_len;
 } mdb_user_index_info;
 
-/* counters of the last search call on a context (for GB/s accounting) */
+/* counters of the last search call on a context (for GB/s accounting)
+ *
+ * mdb_stats: the contract (tests/test_gpu_stats.py holds every sentence; tests/stats_model.py restates it on the host).
+ *
+ * mdb_get_stats waits for the context's stream and reports the LAST search call that launched work on the context, whatever kind of
+ * index the calls before it searched; reading does not reset anything, and a second read returns the same four numbers.  The
+ * numbers do not depend on how the call was made (MDB_MEM_HOST, MDB_MEM_DEVICE read before or after mdb_sync, *_submit + mdb_wait),
+ * on the kernel forms the options select, on mdb_set_profiling, or on the HNSW frontier form's fallback.
+ *
+ *   scored_vectors   flat: b * n.  Posting-list scans (IVF, SPANN, multi-user SPANN): the entries of the probed lists whose
+ *                    distance (or, in a bound-filtered PQ scan, distance bound) the scan evaluates — an entry whose point is
+ *                    tombstoned or dropped by the query's allow bitmap is skipped BEFORE the distance and is not counted; a list
+ *                    named m times in a query's probe row is scanned, and counted, m times; an unknown user scans nothing.
+ *                    HNSW: 0.
+ *   distance_evals,  the graph traversal's, summed over the batch: HNSW, and the centroid graphs of SPANN / multi-user SPANN
+ *   expanded_nodes   (an unknown user traverses nothing).  Flat and IVF: 0.
+ *   algorithmic_bytes
+ *                    flat:  n * d * 4 + b * d * 4 + b * k * 8
+ *                    HNSW:  distance_evals * (row + 4) + expanded_nodes * 16, row = d * 4 (f32 rows) or m (PQ codes of m bytes)
+ *                    IVF:   scored_vectors * (row + 4), row = d * 4 (f32 lists) or m (PQ lists)
+ *                    SPANN: distance_evals * (d * 4 + 4) + expanded_nodes * 16 + scored_vectors * (row + 4): the centroid graph
+ *                           is always f32, row is the posting lists'
+ *
+ * Shards: mdb_ivf_search_shard and mdb_multi_spann_search_shard report what THIS handle did — the scored entries of the lists it
+ * holds, so the ranks' scored_vectors sum to the unsharded call's, and the whole centroid-graph counters on every rank (the
+ * graphs are replicated).  A single IVF index spreads its lists over the ranks by size (longest first, each to the rank with the
+ * fewest entries so far); a multi-user collection keeps list c of every user on rank c % world.  mdb_spann_search_shard (a
+ * single-user handle holds every list) reports what mdb_spann_search does.  The two halves of a multi-user call: after
+ * mdb_multi_spann_probes the centroid graphs' counters and their bytes with scored_vectors 0, after
+ * mdb_multi_spann_search_shard_probes this rank's scored entries and their bytes with the graph counters 0.  mdb_ivf_merge_shards,
+ * mdb_multi_spann_merge_shards and mdb_ivf_find_nearest_centroids are not search calls: they leave the last search call's stats
+ * in place.
+ *
+ * Calls that do no search: b == 0 returns at once, and a call refused on the host (the Limits table below, a filter of the wrong
+ * shape) launches nothing; both leave the previous call's stats untouched.  An IVF call with k == 0 IS a search: it scans its
+ * lists and counts them as with any other k.  What the other families report after k == 0 is outside this contract.  A call
+ * that fails on the device (MDB_ERR_NAN) ran to its end: the stats are that call's, counted as if it had succeeded. */
 typedef struct {
     uint64_t scored_vectors;    /* posting-list / flat vectors scored */
     uint64_t distance_evals;    /* HNSW distance evaluations */

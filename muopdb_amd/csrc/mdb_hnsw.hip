@@ -1670,6 +1670,8 @@ static mdb_status hnsw_ann_search_impl(mdb_hnsw* h, const float* queries, size_t
     if (b == 0) return MDB_OK;
     SubmitScope submit_scope(ctx, submit && mem == MDB_MEM_HOST);
     if (k > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
+    // (hnsw_route refuses the same ef: here, before the context's mdb_stats state is touched — a refused call leaves the last call's)
+    if (ef > MDB_MAX_K * 2) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "ef=%u exceeds %d", ef, MDB_MAX_K * 2);
     float* dq;
     int qstride;
     if (mem == MDB_MEM_DEVICE && s.kind != MDB_QUANT_PQ && s.dimension % 4 == 0 && ((uintptr_t)queries & 15) == 0) {

@@ -108,6 +108,9 @@ static mdb_status spann_search_impl(SpannSet& s, const float* queries, size_t b,
     const size_t k = params->top_k;
     const size_t nexp = params->num_explored_centroids < 0 ? k : (size_t)params->num_explored_centroids;
     if (k > MDB_MAX_K || nexp > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "top_k / num_explored_centroids exceed MDB_MAX_K=%d", MDB_MAX_K);
+    // (the centroid graph's search refuses the same ef: here, before the counters are cleared — a refused call leaves the last call's mdb_stats)
+    if (!(pio && !pio->out) && params->ef_construction > MDB_MAX_K * 2)
+        return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "ef=%u exceeds %d", params->ef_construction, MDB_MAX_K * 2);
     float* dq;
     int qstride;
     MDB_TRY(stage_queries(ctx, queries, b, (int)s.ivf.num_features, mem, (b + 3) / 4 * 4, &dq, &qstride));
