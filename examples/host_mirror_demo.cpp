@@ -116,6 +116,14 @@ static int run_segments(int argc, char** argv) {
     return 0;
 }
 
+// The exact ground truth of a filtered search: the flat index under the planner's bitmap over ROW ids (not run by this demo; it keeps
+// muopdb::FlatIndex compiled with every build).
+muopdb::FlatIndex::Rows flat_ground_truth(muopdb::Device& dev, const std::vector<float>& base, size_t d, const float* queries, size_t b,
+                                          size_t k, const std::vector<uint32_t>& planner) {
+    muopdb::FlatIndex flat(dev, base.data(), base.size() / d, d);
+    return planner.empty() ? flat.search(queries, b, k) : flat.search_filtered(queries, b, k, planner);
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && std::string(argv[1]) == "segments") {
         try { return run_segments(argc, argv); }

@@ -124,7 +124,10 @@ typedef struct {
  * Calls that do no search: b == 0 returns at once, and a call refused on the host (the Limits table below, a filter of the wrong
  * shape) launches nothing; both leave the previous call's stats untouched.  An IVF call with k == 0 IS a search: it scans its
  * lists and counts them as with any other k.  What the other families report after k == 0 is outside this contract.  A call
- * that fails on the device (MDB_ERR_NAN) ran to its end: the stats are that call's, counted as if it had succeeded. */
+ * that fails on the device (MDB_ERR_NAN) ran to its end: the stats are that call's, counted as if it had succeeded.
+ *
+ * mdb_flat_search_filtered: scored_vectors = the allowed rows below n, summed over the queries; algorithmic_bytes =
+ * scored_vectors * d * 4 + b * d * 4 + b * k * 8; the graph counters are 0. */
 typedef struct {
     uint64_t scored_vectors;    /* posting-list / flat vectors scored */
     uint64_t distance_evals;    /* HNSW distance evaluations */
@@ -148,7 +151,7 @@ typedef struct mdb_multi_spann mdb_multi_spann;
  * tests/test_gpu_async_stream.py).
  *
  * | entry point | limit | past it |
- * | mdb_flat_search, mdb_flat_topk | k <= 2048 | MDB_ERR_UNSUPPORTED |
+ * | mdb_flat_search, mdb_flat_search_filtered, mdb_flat_topk | k <= 2048 | MDB_ERR_UNSUPPORTED |
  * | mdb_ivf_search, _search_filtered, _search_points, _search_submit, _search_shard | k <= 2048 | MDB_ERR_UNSUPPORTED |
  * | mdb_ivf_search* with probes == NULL, mdb_ivf_find_nearest_centroids | num_probes <= min(2048, num_clusters) | MDB_ERR_UNSUPPORTED above 2048, MDB_ERR_OUT_OF_RANGE above num_clusters or at 0 |
  * | mdb_ivf_search* with explicit probes | any number of probe columns | - |
@@ -262,6 +265,15 @@ mdb_status mdb_flat_create(mdb_ctx* ctx, const float* base, size_t n, size_t d, 
 void mdb_flat_free(mdb_flat* flat);
 mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_t k, mdb_mem mem, uint32_t* ids_out,
                            float* dist_out, uint32_t* counts_out);
+/* mdb_flat_search under a per-call allow bitmap over ROW ids (the contract of mdb_ivf_search_filtered): bit r of bitmap i keeps row r
+ * for query i; `allow` lives where `mem` says, laid out [n_bitmaps][words_per_bitmap]; n_bitmaps == 1 is one bitmap for every
+ * query, otherwise at least b; words_per_bitmap >= ceil(n / 32) — anything shorter, or 1 < n_bitmaps < b, is MDB_ERR_INVALID_ARG
+ * before any launch; bits at positions >= n are ignored; allow == NULL is mdb_flat_search.  A row that is not allowed is skipped
+ * BEFORE its distance: a NaN in a row that no query allows is not MDB_ERR_NAN, one in an allowed row is.  Rows come ordered by
+ * (distance, row) with the distance bits mdb_flat_search gives the same row; a short row is padded with UINT32_MAX / +inf and
+ * counts_out = min(k, allowed rows).  Every batch size takes the exact scan; an MDB_MEM_DEVICE call only enqueues. */
+mdb_status mdb_flat_search_filtered(mdb_flat* flat, const float* queries, size_t b, size_t k, mdb_mem mem, const uint32_t* allow,
+                                    size_t n_bitmaps, size_t words_per_bitmap, uint32_t* ids_out, float* dist_out, uint32_t* counts_out);
 /* one-shot convenience: create + search + free, host buffers */
 mdb_status mdb_flat_topk(mdb_ctx* ctx, const float* base, size_t n, size_t d, const float* queries, size_t b,
                          mdb_metric metric, size_t k, uint32_t* ids_out, float* dist_out);

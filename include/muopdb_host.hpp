@@ -169,6 +169,37 @@ inline void check_bitmaps(const std::vector<uint32_t>& bitmaps, size_t n_bitmaps
 }
 }  // namespace detail
 
+// The exact scan of an arbitrary base (mdb_flat_*; the reference has no flat index type): rows ordered by (distance, row).
+class FlatIndex {
+  public:
+    struct Rows {   // [b][k]: UINT32_MAX / +inf past counts[i]
+        std::vector<uint32_t> ids;
+        std::vector<float> dist;
+        std::vector<uint32_t> counts;
+    };
+    FlatIndex(Device& dev, const float* base, size_t n, size_t d, mdb_metric metric = MDB_METRIC_L2) : dev_(dev) {
+        dev_.check(mdb_flat_create(dev.ctx(), base, n, d, metric, MDB_MEM_HOST, &h_));
+    }
+    ~FlatIndex() { mdb_flat_free(h_); }
+    FlatIndex(const FlatIndex&) = delete;
+    Rows search(const float* queries, size_t b, size_t k) { return run(queries, b, k, nullptr, 0, 0); }
+    // under allow bitmaps over ROW ids for THIS call: n_bitmaps == 1 -> shared by every query, else one per query
+    Rows search_filtered(const float* queries, size_t b, size_t k, const std::vector<uint32_t>& bitmaps, size_t n_bitmaps = 1) {
+        detail::check_bitmaps(bitmaps, n_bitmaps, b);
+        return run(queries, b, k, bitmaps.data(), n_bitmaps, bitmaps.size() / n_bitmaps);
+    }
+
+  private:
+    Rows run(const float* queries, size_t b, size_t k, const uint32_t* allow, size_t n_bitmaps, size_t words) {
+        Rows r{std::vector<uint32_t>(b * (k ? k : 1)), std::vector<float>(b * (k ? k : 1)), std::vector<uint32_t>(b)};
+        dev_.check(mdb_flat_search_filtered(h_, queries, b, k, MDB_MEM_HOST, allow, n_bitmaps, words, r.ids.data(), r.dist.data(),
+                                            r.counts.data()));
+        return r;
+    }
+    Device& dev_;
+    mdb_flat* h_ = nullptr;
+};
+
 class BlockBasedIvf {
   public:
     // new_with_offset (index.rs:94-138): `index` / `vectors` are the mmapped files

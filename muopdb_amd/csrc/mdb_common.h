@@ -30,6 +30,7 @@
     X(flat_blocks, "MDB_FLAT_BLOCKS", 0)               /* flat-scan grid target (0 = 1024) */                       \
     X(flat_no_small, "MDB_FLAT_NO_SMALL", 0)           /* bases of <= 1024 tiles, batches <= 4: 0 / 3 flat_small_scan_kernel's sorted lists + merge_few_lists (two launches), 1 the general scan kernel, 2 unordered keys + a bound over 1024 thread groups, 4 flat_small_block_kernel (ONE launch, a ticket per block of 16 tiles; measured slower) */ \
     X(flat_no_mfma, "MDB_FLAT_NO_MFMA", 0)             /* exact flat kernels only */                                \
+    X(flat_allow_dense, "MDB_FLAT_ALLOW_DENSE", 16)    /* mdb_flat_search_filtered: a 64-row tile with at least this many allowed rows is scanned in place, a sparser one row by row from the pending ring (0: every non-empty tile in place, 65: every one row by row) */ \
     X(flat_rows, "MDB_FLAT_ROWS", 1)                   /* flat index: keep a row-major copy of the base for the refine's gathers (+ n d 4 bytes) */ \
     X(flat_rows_max_mb, "MDB_FLAT_ROWS_MAX_MB", 8192)   /* ... only for stores up to this many MB of f32 rows (flat bases and large coarse quantizers): above it the refine gathers from the tile store and the index stays at ~1.5 x its rows */ \
     X(no_inplace, "MDB_NO_INPLACE", 0)                 /* device-resident query rows are always copied into padded staging rows */ \

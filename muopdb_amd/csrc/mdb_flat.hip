@@ -11,6 +11,7 @@
 #include "mdb_device.hip.h"
 #include "mdb_kernels.h"
 #include "mdb_launch.hip.h"
+#include "mdb_flat_allow.hip.h"
 
 // ------------------------------------------------------------------------------------------ relayout
 __global__ __launch_bounds__(256) void rows_to_tiles_kernel(const float* __restrict__ rows, size_t n, int d, int d4,
@@ -95,11 +96,13 @@ mdb_status stage_queries(mdb_ctx* ctx, const float* queries, size_t b, int d, md
 
 // ------------------------------------------------------------------------------------------ scan
 // grid (nblk, ceil(B/QT)); block = 4 waves = 4 tiles per round; QT queries share every load.
+// The allow-bitmap mode (mdb_flat_allow.hip.h) shares the kernel's register budget: without a floor the four-query form went from 157 to
+// 181 VGPRs, three waves per SIMD to two, for the unfiltered scan as well; with the floor it stays at three (156).
 template <int METRIC, int QT>
 __global__ __launch_bounds__(MDB_BLOCK) void flat_scan_kernel(const float4* __restrict__ tiles, size_t n, size_t ntiles,
                                                               DistPlan p, const float* __restrict__ q, int qstride, int k,
                                                               uint64_t* __restrict__ partial, uint32_t* __restrict__ flags,
-                                                              const uint32_t* __restrict__ gate) {
+                                                              const uint32_t* __restrict__ gate, FlatAllow fa) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     if (gate && *gate == 0) return;  // fallback launch of the batched path: nothing overflowed
     BlockSelect<MDB_BLOCK> sel[QT];
@@ -110,27 +113,51 @@ __global__ __launch_bounds__(MDB_BLOCK) void flat_scan_kernel(const float4* __re
     const size_t q0 = (size_t)blockIdx.y * QT;
     const float* qb = q + q0 * qstride;
     const size_t ngroups = (ntiles + 3) / 4;
-    bool nan_seen = false;
-    for (size_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        size_t tile = g * 4 + wave;
-        size_t v = tile * MDB_TILE + lane;
-        bool valid = tile < ntiles && v < n;
+    bool nan_seen = false, first = true;
+    // ONE loop for both modes.  Without a bitmap: group g's four tiles, lane = row.  Under a per-call allow bitmap the mode
+    // (mdb_flat_allow.hip.h) chooses the row of every lane — a dense tile's, or one queued by a sparse tile — and whether the group runs
+    // a round at all
+    FlatAllowRun run;
+    if (fa.bits) flat_allow_begin<QT>(fa, run, n, q0, lds + QT * sel_bytes, sel[0].spare());
+    for (size_t g = blockIdx.x;; g += gridDim.x) {
+        const float4* row;
+        uint32_t v = 0;
+        bool have = false;
+        if (fa.bits) {
+            const int act = flat_allow_group<QT>(fa, run, lds + QT * sel_bytes, g, ngroups, n, ntiles, q0, v, have);
+            if (act == FLAT_ALLOW_DONE) break;
+            if (act == FLAT_ALLOW_NO_ROUND) continue;
+            row = tiles + (size_t)(v / MDB_TILE) * p.d4 * MDB_TILE + v % MDB_TILE;
+        } else {
+            if (g >= ngroups) break;
+            const size_t tile = g * 4 + wave;
+            const size_t vv = tile * MDB_TILE + lane;
+            have = tile < ntiles && vv < n;
+            v = (uint32_t)vv;
+            row = tiles + tile * (size_t)p.d4 * MDB_TILE + lane;
+        }
         float raw[QT];
-        if (valid) {
-            TileLoader ld{tiles + tile * (size_t)p.d4 * MDB_TILE + lane};
+        uint32_t bit[QT];
+        if (have) {
+            TileLoader ld{row};
             exact_sums<METRIC, QT, TileLoader, 2>(ld, qb, qstride, p, raw);
+            if (fa.bits) {
+                __builtin_amdgcn_sched_barrier(0);   // the bit loads stay behind the sums
+                flat_allow_row_bits<QT>(fa, run, q0, v, bit);
+            }
         }
 #pragma unroll
         for (int i = 0; i < QT; ++i) {
             uint64_t key = MDB_KEY_MAX;
-            if (valid) {
+            if (have && (!fa.bits || bit[i])) {
                 float dist = finish_distance<METRIC>(raw[i]);
                 if (dist != dist) nan_seen = true;
-                key = make_key(dist, (uint32_t)v);
+                key = make_key(dist, v);
             }
-            if (g == blockIdx.x) sel[i].warm_start(key);  // first round: threshold from the waves' own k-th keys
+            if (first) sel[i].warm_start(key);  // the first round that runs: threshold from the waves' own k-th keys
             sel[i].offer(key);
         }
+        first = false;
 #pragma unroll
         for (int i = 0; i < QT; ++i) sel[i].round_end();
     }
@@ -677,12 +704,12 @@ mdb_status unpack_keys(mdb_ctx* ctx, const uint64_t* d_keys, size_t total, uint3
 template <int METRIC>
 static mdb_status launch_flat_scan(mdb_ctx* ctx, const TileView& ts, const DistPlan& p, const float* dq, int qstride,
                                    size_t b, size_t bpad, int qt, int k, unsigned nblk, uint64_t* partial,
-                                   const uint32_t* gate) {
+                                   const uint32_t* gate, const FlatAllow& allow) {
     dim3 grid(nblk, (unsigned)(bpad / qt));
-    size_t lds = BlockSelect<MDB_BLOCK>::lds_bytes(k) * qt;
+    size_t lds = BlockSelect<MDB_BLOCK>::lds_bytes(k) * qt + (allow.bits ? FLAT_ALLOW_LDS : 0);   // (flat_choose_qt's 60 KB leave room for the ring)
     const float4* tiles = (const float4*)ts.data;
     MDB_TRY(mdb_pick<4, 2, 1>(qt, [&](auto QT) {
-        return mdb_launch(ctx, flat_scan_kernel<METRIC, QT()>, grid, MDB_BLOCK, lds, tiles, ts.n, ts.ntiles, p, dq, qstride, k, partial, ctx->d_flags, gate);
+        return mdb_launch(ctx, flat_scan_kernel<METRIC, QT()>, grid, MDB_BLOCK, lds, tiles, ts.n, ts.ntiles, p, dq, qstride, k, partial, ctx->d_flags, gate, allow);
     }));
     MDB_HIP(ctx, hipGetLastError());
     return MDB_OK;
@@ -699,7 +726,9 @@ static int flat_choose_qt(const mdb_ctx* ctx, size_t b, int k) {
 }
 
 mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const float* dq, int qstride, size_t b, size_t k,
-                          uint64_t* d_keys, uint32_t* d_counts, bool profile, const uint32_t* gate, const UnpackOut* unpack) {
+                          uint64_t* d_keys, uint32_t* d_counts, bool profile, const uint32_t* gate, const UnpackOut* unpack,
+                          const FlatAllow* allow) {
+    const FlatAllow fa = allow ? *allow : FlatAllow{};
     if (b == 0) return MDB_OK;
     if (k > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
     int qt = flat_choose_qt(ctx, b, (int)k);
@@ -710,7 +739,7 @@ mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const fl
     DistPlan p = make_plan(ts.d, metric);
     // small base, a handful of queries: one wave per (tile, query), every load in flight, lists merged by bound + rank
     if (b <= 4 && k >= 1 && k <= 64 && ts.ntiles >= 1 && ts.ntiles <= 1024 && p.n16 >= 1 && p.n16 <= 8 && p.n8 == 0 && p.n4 == 0 && p.ntail == 0 &&
-        !gate && ctx->opt.flat_no_small != 1) {
+        !gate && !fa.bits && ctx->opt.flat_no_small != 1) {
         void* partial;
         MDB_TRY(mdb_scratch(ctx, (size_t)ts.ntiles * b * MDB_TILE * 8, &partial));
         const bool sorted = ctx->opt.flat_no_small != 2;   // 2: the waves store their keys unordered, the merge bounds 1024 thread groups (measured slower)
@@ -771,11 +800,11 @@ mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const fl
     ProfScope prof(ctx);
     ctx->prof_on = saved;
     if (metric == MDB_METRIC_L2)
-        MDB_TRY(launch_flat_scan<MDB_METRIC_L2>(ctx, ts, p, dq, qstride, b, bpad, qt, (int)k, nblk, (uint64_t*)partial, gate));
+        MDB_TRY(launch_flat_scan<MDB_METRIC_L2>(ctx, ts, p, dq, qstride, b, bpad, qt, (int)k, nblk, (uint64_t*)partial, gate, fa));
     else if (metric == MDB_METRIC_L2SQ)
-        MDB_TRY(launch_flat_scan<MDB_METRIC_L2SQ>(ctx, ts, p, dq, qstride, b, bpad, qt, (int)k, nblk, (uint64_t*)partial, gate));
+        MDB_TRY(launch_flat_scan<MDB_METRIC_L2SQ>(ctx, ts, p, dq, qstride, b, bpad, qt, (int)k, nblk, (uint64_t*)partial, gate, fa));
     else
-        MDB_TRY(launch_flat_scan<MDB_METRIC_DOT>(ctx, ts, p, dq, qstride, b, bpad, qt, (int)k, nblk, (uint64_t*)partial, gate));
+        MDB_TRY(launch_flat_scan<MDB_METRIC_DOT>(ctx, ts, p, dq, qstride, b, bpad, qt, (int)k, nblk, (uint64_t*)partial, gate, fa));
     }
     launch_merge_keys(ctx, (const uint64_t*)partial, (size_t)nblk * k, b, k, d_keys, d_counts, gate, unpack);
     MDB_HIP(ctx, hipGetLastError());
@@ -832,16 +861,41 @@ void mdb_flat_free(mdb_flat* flat) {
     mdb_ctx_release(ctx);
 }
 
-mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_t k, mdb_mem mem, uint32_t* ids_out,
-                           float* dist_out, uint32_t* counts_out) {
+// mdb_flat_search and, with `allow`, mdb_flat_search_filtered
+static mdb_status flat_search_impl(mdb_flat* flat, const float* queries, size_t b, size_t k, mdb_mem mem, const uint32_t* allow,
+                                   size_t n_bitmaps, size_t words, uint32_t* ids_out, float* dist_out, uint32_t* counts_out) {
     if (!flat || (!queries && b) || !ids_out || !dist_out) return MDB_ERR_INVALID_ARG;
     mdb_ctx* ctx = flat->ctx;
     MDB_ENTER(ctx);
     if (b == 0) return MDB_OK;
     if (k > MDB_MAX_K) return mdb_fail(ctx, MDB_ERR_UNSUPPORTED, "k=%zu exceeds MDB_MAX_K=%d", k, MDB_MAX_K);
+    FlatAllow fa;
+    if (allow) {
+        // a bitmap covers every row, a per-query set every query of the batch: anything shorter would be read out of bounds
+        if (n_bitmaps == 0 || words < (flat->ts.n + 31) / 32)
+            return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "filter bitmaps of %zu words do not cover %zu rows", n_bitmaps ? words : (size_t)0, flat->ts.n);
+        if (n_bitmaps != 1 && n_bitmaps < b)
+            return mdb_fail(ctx, MDB_ERR_INVALID_ARG, "%zu filter bitmaps for a batch of %zu queries", n_bitmaps, b);
+        MDB_TRY(mdb_require_idle(ctx, mem));
+        fa.bits = allow;
+        const size_t bytes = (n_bitmaps == 1 ? 1 : b) * words * 4;
+        if (mem == MDB_MEM_HOST && bytes) {
+            void *pin, *dev;
+            MDB_TRY(mdb_pinned(ctx, MDB_PIN_FILTER, bytes, &pin));
+            memcpy(pin, allow, bytes);
+            MDB_TRY(mdb_scratch(ctx, bytes, &dev));
+            MDB_HIP(ctx, hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, ctx->stream));
+            fa.bits = (const uint32_t*)dev;
+        }
+        fa.stride = n_bitmaps == 1 ? 0 : words;
+        fa.dense = (uint32_t)std::max<long long>(0, std::min<long long>(ctx->opt.flat_allow_dense, 65));
+        fa.nq = (uint32_t)b;
+        fa.scored = ctx->d_counters + 2;
+    }
     float* dq;
     int qstride;
-    const bool batched = flat_mfma_applicable(ctx, view_of(flat->ts), flat->aux, b, k);
+    // (under a bitmap every batch takes the exact scan: the matrix-core filter has no filtered form)
+    const bool batched = !allow && flat_mfma_applicable(ctx, view_of(flat->ts), flat->aux, b, k);
     // whole query groups of the matrix-core filter (up to 8 x 32 rows) / of the exact scan (flat_choose_qt: one query is its own group)
     const size_t bpad = batched ? (b + 255) / 256 * 256 : (b == 1 ? 1 : (b + 3) / 4 * 4);
     MDB_TRY(stage_queries(ctx, queries, b, flat->ts.d, mem, bpad, &dq, &qstride));
@@ -859,16 +913,27 @@ mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_
         // device outputs: the merge kernel writes the caller's rows itself (scan + merge are the only two launches)
         UnpackOut up{ids_out, dist_out, counts_out};
         fused = mem == MDB_MEM_DEVICE && k > 0;
+        if (allow) {   // the scan counts the allowed rows itself (device calls only enqueue: the host never sees the bitmaps' bits)
+            if (!ctx->counters_clean) MDB_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, 32, ctx->stream));
+            ctx->counters_clean = false;
+        }
         MDB_TRY(flat_topk_keys(ctx, view_of(flat->ts), flat->metric, dq, qstride, b, k, (uint64_t*)keys, (uint32_t*)cnts, true, nullptr,
-                               fused ? &up : nullptr));
+                               fused ? &up : nullptr, allow ? &fa : nullptr));
     }
     // one pass = N*d*4 B read once per batch + queries + outputs
     ctx->stats = mdb_stats{};
     ctx->counter_base = 0;
-    ctx->stats.scored_vectors = (uint64_t)b * flat->ts.n;
-    ctx->dev_counters = false;  // flat scans count on the host (scored = n x b): no counter memset launch on this path
-    ctx->stat_bytes_per_eval = 0; ctx->stat_bytes_per_scored = 0;
-    ctx->stat_fixed_bytes = (uint64_t)flat->ts.n * flat->ts.d * 4 + (uint64_t)b * flat->ts.d * 4 + (uint64_t)b * k * 8;
+    ctx->stat_bytes_per_eval = 0;
+    if (allow) {   // only the allowed rows are fetched
+        ctx->dev_counters = true;
+        ctx->stat_bytes_per_scored = (uint64_t)flat->ts.d * 4;
+        ctx->stat_fixed_bytes = (uint64_t)b * flat->ts.d * 4 + (uint64_t)b * k * 8;
+    } else {
+        ctx->stats.scored_vectors = (uint64_t)b * flat->ts.n;
+        ctx->dev_counters = false;  // flat scans count on the host (scored = n x b): no counter memset launch on this path
+        ctx->stat_bytes_per_scored = 0;
+        ctx->stat_fixed_bytes = (uint64_t)flat->ts.n * flat->ts.d * 4 + (uint64_t)b * flat->ts.d * 4 + (uint64_t)b * k * 8;
+    }
     size_t total = b * k;
     if (mem == MDB_MEM_DEVICE) {
         if (fused) return MDB_OK;
@@ -884,6 +949,16 @@ mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_
     MDB_HIP(ctx, hipGetLastError());
     const HostCopy back[3] = {{ids_out, dids, total * 4}, {dist_out, ddist, total * 4}, {counts_out, cnts, b * 4}};
     return mdb_return_to_host(ctx, back, 3);
+}
+
+mdb_status mdb_flat_search(mdb_flat* flat, const float* queries, size_t b, size_t k, mdb_mem mem, uint32_t* ids_out,
+                           float* dist_out, uint32_t* counts_out) {
+    return flat_search_impl(flat, queries, b, k, mem, nullptr, 0, 0, ids_out, dist_out, counts_out);
+}
+
+mdb_status mdb_flat_search_filtered(mdb_flat* flat, const float* queries, size_t b, size_t k, mdb_mem mem, const uint32_t* allow,
+                                    size_t n_bitmaps, size_t words_per_bitmap, uint32_t* ids_out, float* dist_out, uint32_t* counts_out) {
+    return flat_search_impl(flat, queries, b, k, mem, allow, n_bitmaps, words_per_bitmap, ids_out, dist_out, counts_out);
 }
 
 mdb_status mdb_flat_topk(mdb_ctx* ctx, const float* base, size_t n, size_t d, const float* queries, size_t b,

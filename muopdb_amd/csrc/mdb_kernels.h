@@ -28,9 +28,18 @@ struct UnpackOut {
 // bytes must fit 48 KB of LDS.
 mdb_status merge_sorted_rows(mdb_ctx* ctx, const uint64_t* d_rows, size_t rows, size_t k, size_t b, uint64_t* d_out, uint32_t* d_counts,
                              uint32_t* d_ids32, const UnpackOut* unpack);
+// per-call allow bitmaps over ROW ids (mdb_flat_search_filtered; mdb_flat_allow.hip.h): bit r of bitmap i keeps row r for query i.
+// With `bits` set every batch takes flat_scan_kernel (no small-base kernels).
+struct FlatAllow {
+    const uint32_t* bits = nullptr;        // device; nullptr: no filter
+    size_t stride = 0;                     // words between the queries' bitmaps (0: one bitmap for every query); a bitmap covers ceil(n / 32) words
+    uint32_t dense = 0;                    // a tile with at least this many live rows is scanned in place, a sparser one row by row (MDB_FLAT_ALLOW_DENSE)
+    uint32_t nq = 0;                       // queries of the batch (the padding rows of the last query group have no bitmap)
+    unsigned long long* scored = nullptr;  // device counter += allowed rows below n, summed over the queries (may be null)
+};
 mdb_status flat_topk_keys(mdb_ctx* ctx, const TileView& ts, int metric, const float* d_queries_padded, int qstride,
                           size_t b, size_t k, uint64_t* d_keys, uint32_t* d_counts, bool profile = false,
-                          const uint32_t* gate = nullptr, const UnpackOut* unpack = nullptr);
+                          const uint32_t* gate = nullptr, const UnpackOut* unpack = nullptr, const FlatAllow* allow = nullptr);
 
 // ---- mdb_flat_mfma.hip: batched flat scan = exact top-k of a strided sample + MFMA filter + exact refine
 // (same keys as flat_topk_keys, bit for bit).  FlatAux is built once per store by flat_build_aux (stays

@@ -206,16 +206,45 @@ class FlatIndex:
         except Exception:
             pass
 
-    def search(self, queries, k):
+    def search(self, queries, k, allow=None):
+        """allow: per-call filter over ROW ids (mdb_flat_search_filtered) — a numpy array, bool [n] / [b][n] or packed uint32 [words] /
+        [b][words] as BlockBasedIvf.search takes its planner bitmaps, or a torch CUDA tensor of either kind: the call then runs on
+        device memory and the rows come back after mdb_sync."""
         q = L.f32(queries).reshape(-1, self.d)
         b = q.shape[0]
+        if allow is not None and not isinstance(allow, np.ndarray) and hasattr(allow, "data_ptr"):
+            return self._search_allow_device(q, b, k, allow)
         ids = np.empty((b, max(k, 1)), np.uint32)
         dist = np.empty((b, max(k, 1)), np.float32)
         counts = np.zeros(b, np.uint32)
-        self.ctx.check(self.ctx.lib.mdb_flat_search(self.h, L.ptr(q, C.c_float), C.c_size_t(b), C.c_size_t(k),
-                                                    C.c_int(L.MEM_HOST), L.ptr(ids, C.c_uint32),
-                                                    L.ptr(dist, C.c_float), L.ptr(counts, C.c_uint32)))
+        if allow is None:
+            self.ctx.check(self.ctx.lib.mdb_flat_search(self.h, L.ptr(q, C.c_float), C.c_size_t(b), C.c_size_t(k),
+                                                        C.c_int(L.MEM_HOST), L.ptr(ids, C.c_uint32),
+                                                        L.ptr(dist, C.c_float), L.ptr(counts, C.c_uint32)))
+        else:
+            ap, nb, words, keep = _planner_args(pack_allow(allow))
+            self.ctx.check(self.ctx.lib.mdb_flat_search_filtered(self.h, L.ptr(q, C.c_float), b, k, L.MEM_HOST, ap, nb, words,
+                                                                 L.ptr(ids, C.c_uint32), L.ptr(dist, C.c_float), L.ptr(counts, C.c_uint32)))
         return ids[:, :k], dist[:, :k], counts
+
+    def _search_allow_device(self, q, b, k, allow):
+        import torch
+        dev = allow.device
+        if allow.dtype == torch.bool:   # bit r of word r >> 5, rows padded to whole words
+            bits = torch.nn.functional.pad(allow, (0, (-allow.shape[-1]) % 32)).reshape(*allow.shape[:-1], -1, 8).to(torch.uint8)
+            weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=dev)
+            allow = (bits * weights).sum(-1, dtype=torch.uint8).contiguous().view(torch.int32)   # four bytes, lowest first, are a word
+        allow = allow.contiguous()
+        nb, words = (1, allow.shape[0]) if allow.dim() == 1 else allow.shape
+        dq = torch.from_numpy(q).to(dev)
+        ids = torch.empty((b, max(k, 1)), dtype=torch.int32, device=dev)
+        dist = torch.empty((b, max(k, 1)), dtype=torch.float32, device=dev)
+        counts = torch.zeros(b, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)   # the inputs were made on torch's stream, the call runs on the context's
+        self.ctx.check(self.ctx.lib.mdb_flat_search_filtered(self.h, dq.data_ptr(), b, k, L.MEM_DEVICE, allow.data_ptr(), nb, words,
+                                                             ids.data_ptr(), dist.data_ptr(), counts.data_ptr()))
+        self.ctx.sync()
+        return ids.cpu().numpy().view(np.uint32)[:, :k], dist.cpu().numpy()[:, :k], counts.cpu().numpy().view(np.uint32)
 
     def search_device(self, q_ptr, b, k, ids_ptr, dist_ptr, counts_ptr=None):
         """Device-resident queries / outputs (torch tensors' data_ptr()); enqueue only."""
@@ -256,6 +285,15 @@ def allow_bitmap(point_ids, num_points):
     p = np.asarray(point_ids, np.int64)
     np.bitwise_or.at(bm, p >> 5, (np.uint32(1) << (p & 31).astype(np.uint32)))
     return bm
+
+
+def pack_allow(allow):
+    """bool rows [n] / [b][n] -> uint32 bitmaps [words] / [b][words] (bit r of word r >> 5); uint32 bitmaps pass as they are."""
+    a = np.asarray(allow)
+    if a.dtype != np.bool_:
+        return np.ascontiguousarray(a, np.uint32)
+    a = np.pad(a, [(0, 0)] * (a.ndim - 1) + [(0, (-a.shape[-1]) % 32)])
+    return np.ascontiguousarray(np.packbits(a, axis=-1, bitorder="little")).view("<u4")
 
 
 def _merge_shards(ctx, call, blocks, b, k, with_found):
